@@ -8,8 +8,10 @@ A "step" = one pass of the hot path over one batch of synthetic input that is al
                   ("hip": libmst.so fp32-MFMA kernels = configs[2];  "torch": PyTorch-ROCm ops = configs[1])
     exchange      all-gather of embeddings + labels over RCCL (N>1) and InfoNCE on the gathered batch
 Prints ONE JSON line on rank 0 (see the driver contract in the task statement), with `roofline` for the
-dominant hand-written kernel (HIP-event timed inside the timed region) and `cpu_baseline` (the CPU oracle
-timed on the host cores on a bounded sample; rank 0, N=1 only).
+dominant hand-written kernel (HIP-event timed inside the timed region).  A plain run does only that: set up, warm up,
+time --steps steps, write --dump-outputs, print the line.  `--full` adds what the line does not need: the post-timing
+correctness checks (`config.verified`), `cpu_baseline` (the CPU oracle timed on the host cores on a bounded sample;
+rank 0, N=1 only) and the opt-in precision modes (`alt`).
 """
 import argparse
 import json
@@ -40,11 +42,18 @@ def parse():
     ap.add_argument("--encoder", choices=["hip", "torch"], default="hip",
                     help="hip (default, configs[2]): stage B on libmst.so's hand-written kernels; a missing / refusing HIP encoder is "
                          "an error, never a library fallback.  torch: BASELINE configs[1], stage B on PyTorch-ROCm (explicit opt-in)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, run what the result line's headline does not need: the post-timing correctness "
+                         "check (config.verified), the CPU oracle baseline (cpu_baseline) and the opt-in precision modes (alt)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after timing, write what the timed path computed in its last step (rank 0) as DIR/<name>.npy in "
+                         "float32: embeddings, loss and, on the forward path, features; the inputs are seeded, so the same "
+                         "arguments give the same inputs in every run")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the post-timing correctness check of the timed workload (config.verified)")
+                    help="--full: skip the post-timing correctness check of the timed workload (config.verified)")
     ap.add_argument("--verify-b1", action="store_true",
-                    help="config.verified: besides the re-ordered batches, also run every clip alone (B = 1) and compare bit for bit")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full, config.verified: besides the re-ordered batches, also run every clip alone (B = 1) and compare bit for bit")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out cpu_baseline")
     ap.add_argument("--precision", choices=["fp32", "f16x3", "f16x3-all", "f16"], default="fp32",
                     help="conv1 arithmetic: exact fp32 MFMA (default) or opt-in 3-term split-precision f16 MFMA")
     ap.add_argument("--aug", action="store_true", help="also run the augmentation chain on the negative clip of every triplet inside the timed step (BASELINE configs[3] without SCNet)")
@@ -73,7 +82,28 @@ def parse():
     ap.add_argument("--ingest", choices=["resident", "f32", "pcm16"], default="resident",
                     help="resident (default, the contract: inputs in HBM before timing) | f32 | pcm16: every step's batch "
                          "comes from pinned host memory over PCIe (double-buffered, overlapped); PCIe-inclusive rate")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.verify_b1 and not a.full:
+        ap.error("--verify-b1 is part of the --full checks")
+    return a
+
+
+DUMP_BYTES = 60_000_000   # --dump-outputs: the per-clip arrays together stay below this (64 MB with the scalars and headers)
+
+
+def dump_outputs(d, per_clip, scalars):
+    """--dump-outputs DIR: the last timed step's outputs as DIR/<name>.npy, float32.  The per-clip arrays share their first
+    axis; if together they exceed DUMP_BYTES, the same fixed, seeded sample of clips is written from each."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    rows = {k: v.detach().float().cpu().numpy() for k, v in per_clip.items()}
+    n = next(iter(rows.values())).shape[0]
+    keep = min(n, DUMP_BYTES // sum(v[:1].nbytes for v in rows.values()))
+    pick = np.sort(np.random.default_rng(0).choice(n, keep, replace=False)) if keep < n else slice(None)
+    for k, v in rows.items():
+        np.save(os.path.join(d, k + ".npy"), v[pick])
+    for k, v in scalars.items():
+        np.save(os.path.join(d, k + ".npy"), v.detach().float().cpu().numpy())
 
 
 def cpu_baseline(model_sd, x, cfg, budget_s=15.0):
@@ -356,7 +386,7 @@ def main():
             if timed:
                 evs[11].record()
                 marks.append((e0, e1, e2, kev, evs[11], crit.gather_events))
-            last["emb"] = emb
+            last["emb"], last["feats"] = emb, feats
             return loss
 
     if a.train:   # training step: same data, same metric unit; reported with its own workload string
@@ -394,7 +424,7 @@ def main():
                 scaler.update()
             else:
                 opt.step()
-            return loss
+            return emb, loss
         for _ in range(max(a.warmup, 5)):
             train_step()
         if world > 1:
@@ -402,7 +432,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(a.steps):
-            loss = train_step()
+            emb, loss = train_step()
         crit_t.finish()
         if world > 1:
             dist.barrier()
@@ -410,6 +440,8 @@ def main():
         t = torch.tensor([time.perf_counter() - t0], device=dev, dtype=torch.float64)
         if world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, {"embeddings": emb}, {"loss": loss})
         if rank == 0:
             print(json.dumps({
                 "metric": "triplets/sec (10 s @ 44.1 kHz, 4-stem, bs=24)", "value": round(world * a.triplets * a.steps / t.item(), 3),
@@ -456,13 +488,15 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     el = t.item()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"embeddings": last["emb"], "features": last["feats"]}, {"loss": loss})
 
-    # post-timing check of the timed workload itself (outside the timed region): batch independence on every rank; the oracle
-    # comparison rides on the cpu_baseline leg (rank 0, N = 1), see verify()
+    # --full: post-timing check of the timed workload itself (outside the timed region): batch independence on every rank; the
+    # oracle comparison rides on the cpu_baseline leg (rank 0, N = 1), see verify()
     main_emb = last["emb"].clone()
     oracle_clips = [0, (B // 2) // 3 * 3, B - 1] if B >= 3 else list(range(B))   # first, a middle anchor, the last (a negative under --aug)
     verified, base, ox = None, None, None
-    if not a.no_verify:
+    if a.full and not a.no_verify:
         if rank == 0 and world == 1 and not a.no_cpu_baseline and last["stems"] is not None:
             ox = torch.cat([torch.cat([last["stems"][s][c:c + 1] for s in ("vocals", "bass", "drums", "other")], 1)
                             for c in oracle_clips], 0).float().cpu()
@@ -472,10 +506,10 @@ def main():
             dist.all_reduce(okf, op=dist.ReduceOp.MIN)
         verified["ok_all_ranks"] = bool(okf.item() == 1.0)
 
-    # opt-in precision modes, measured after (outside) the contract's timed region; the headline stays exact fp32
+    # --full: opt-in precision modes, measured after (outside) the contract's timed region; the headline stays exact fp32
     alt = None
     main_marks = len(marks)
-    if backend == "hip" and a.precision == "fp32" and not a.aug and a.ingest == "resident" and a.config == "default":
+    if a.full and backend == "hip" and a.precision == "fp32" and not a.aug and a.ingest == "resident" and a.config == "default":
         notes = {"f16x3-all": "conv1+conv2 on f16 MFMA with 3-term split precision, fp32 accumulate; same 1e-4 parity tests as the exact-fp32 kernels",
                  "f16": "conv1+conv2 with plain f16 operands, fp32 accumulate (the reference's --use_amp conv arithmetic); "
                         "NOT within the 1e-4 parity bar, shown for headroom only"}
@@ -654,14 +688,14 @@ def main():
         out["alt"] = alt
         if multi is not None:
             out["multi_gpu"] = multi
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             cfg = dict(sr=sr, n_fft=n_fft, hop=hop, n_mels=n_mels, split=split, overlap=overlap)
             if ox is None:   # no stems to check against (--ingest / --no-verify): the baseline runs on the synthetic clips themselves
                 ox = x[oracle_clips].float().cpu()
             out["cpu_baseline"], oemb = cpu_baseline(model.state_dict(), ox, cfg)
             if verified is not None and last["stems"] is not None:
                 verify_oracle(verified, main_emb, oracle_clips, oemb, a.precision)
-        out["config"]["verified"] = verified if verified is not None else "skipped (--no-verify)"
+        out["config"]["verified"] = verified if verified is not None else "skipped (--no-verify)" if a.full else "skipped (runs with --full)"
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

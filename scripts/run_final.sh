@@ -5,12 +5,12 @@ out=gpurun_out
 timeout -k 10 1000 python -m pytest tests -m gpu -q > $out/${tag}_tests.log 2>&1; echo rc=$? >> $out/${tag}_tests.log
 grep -E "passed|failed|FAILED|^rc=" $out/${tag}_tests.log | tail -8
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
-python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err || exit 1
-python bench.py --config baseline_sh --no-cpu-baseline > $out/${tag}_bench_sh.json 2>> $out/${tag}_bench.err || exit 1
-python bench.py --config config5 --seconds 30 --triplets 8 --no-cpu-baseline > $out/${tag}_bench_c5.json 2>> $out/${tag}_bench.err || exit 1
-python bench.py --aug --no-cpu-baseline > $out/${tag}_bench_aug.json 2>> $out/${tag}_bench.err || exit 1
-python bench.py --ingest pcm16 --no-cpu-baseline > $out/${tag}_bench_ingest_pcm16.json 2>> $out/${tag}_bench.err || exit 1
-python bench.py --ingest f32 --no-cpu-baseline > $out/${tag}_bench_ingest_f32.json 2>> $out/${tag}_bench.err || exit 1
+python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err || exit 1
+python bench.py --full --config baseline_sh --no-cpu-baseline > $out/${tag}_bench_sh.json 2>> $out/${tag}_bench.err || exit 1
+python bench.py --full --config config5 --seconds 30 --triplets 8 --no-cpu-baseline > $out/${tag}_bench_c5.json 2>> $out/${tag}_bench.err || exit 1
+python bench.py --full --aug --no-cpu-baseline > $out/${tag}_bench_aug.json 2>> $out/${tag}_bench.err || exit 1
+python bench.py --full --ingest pcm16 --no-cpu-baseline > $out/${tag}_bench_ingest_pcm16.json 2>> $out/${tag}_bench.err || exit 1
+python bench.py --full --ingest f32 --no-cpu-baseline > $out/${tag}_bench_ingest_f32.json 2>> $out/${tag}_bench.err || exit 1
 for p in fp32 f16x3 f16 amp; do python bench.py --train --train-precision $p > $out/${tag}_train_$p.json 2>> $out/${tag}_bench.err || exit 1; done
 for p in fp32 f16x3 f16; do python bench.py --train --train-precision $p --config baseline_sh > $out/${tag}_train_sh_$p.json 2>> $out/${tag}_bench.err || exit 1; done
 for p in fp32 f16x3 f16; do python bench.py --train --train-precision $p --config config5 --seconds 30 --triplets 8 > $out/${tag}_train_c5_$p.json 2>> $out/${tag}_bench.err || exit 1; done

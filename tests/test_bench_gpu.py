@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +26,7 @@ def _bench(args, **env):
 
 
 def test_contract_line_hip_encoder():
-    out = _bench(SMALL + ["--verify-b1"])
+    out = _bench(SMALL + ["--full", "--verify-b1"])
     assert out["n_gpus"] == 1 and out["world"] == 1 and out["unit"] == "triplets/s" and out["value"] > 0
     rf = out["roofline"]
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source", "stage_a_hbm_frac", "stage_b_tflops",
@@ -46,10 +47,25 @@ def test_contract_line_hip_encoder():
 
 
 def test_contract_line_with_cpu_baseline_checks_against_the_oracle():
-    out = _bench(["--steps", "2", "--warmup", "1", "--triplets", "2", "--seconds", "2"])
+    out = _bench(["--steps", "2", "--warmup", "1", "--triplets", "2", "--seconds", "2", "--full"])
     v = out["config"]["verified"]
     assert v["ok"] and v["oracle"]["beyond_tol"] == 0 and v["oracle"]["max_rel"] <= 1e-4 and len(v["oracle"]["clips"]) == 3
     assert out["cpu_baseline"]["kind"] == "port" and out["cpu_baseline"]["value"] > 0
+
+
+def test_plain_line_and_its_dumped_outputs_repeat_run_to_run(tmp_path):
+    """Without --full the line carries the headline only; --dump-outputs writes the last timed step's outputs, the same
+    arrays in every run with the same arguments."""
+    args = ["--steps", "3", "--warmup", "1", "--triplets", "2", "--seconds", "2", "--dump-outputs"]
+    outs = [_bench(args + [str(tmp_path / d)]) for d in ("a", "b")]
+    for out in outs:
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["dtype"] == "f32"
+        assert "cpu_baseline" not in out and out["alt"] is None and out["config"]["verified"] == "skipped (runs with --full)"
+    for name, shape in (("embeddings", (6, 768)), ("features", (6, 64)), ("loss", ())):
+        a, b = (np.load(tmp_path / d / f"{name}.npy") for d in ("a", "b"))
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), name
+        assert np.array_equal(a, b), name
+    assert float(np.load(tmp_path / "a" / "loss.npy")) == outs[0]["config"]["loss"]
 
 
 def test_configs1_torch_encoder_line():
@@ -59,7 +75,7 @@ def test_configs1_torch_encoder_line():
 
 
 def test_gpus_2_launches_two_ranks_itself():
-    out = _bench(["--gpus", "2"] + SMALL, MST_BENCH_ONE_GPU="1", MST_BENCH_BACKEND="gloo")
+    out = _bench(["--gpus", "2", "--full"] + SMALL, MST_BENCH_ONE_GPU="1", MST_BENCH_BACKEND="gloo")
     assert out["n_gpus"] == 2 and out["world"] == 2 and out["rccl_ranks_seen"] == 2
     assert out["config"]["parallelism"] == "clip-sharded x2" and "cpu_baseline" not in out
     mg = out["multi_gpu"]
