@@ -1,7 +1,8 @@
 /*
  * mst.h -- C ABI of libmst.so: MI355X (gfx950) kernels for the contrastive data path of
  * barry-mir/mixing-style-transfer (waveform stems -> [augment] -> STFT -> mel -> 64-d mixing
- * features -> FiLM band-split CNN encoder -> embedding -> InfoNCE).
+ * features -> FiLM band-split CNN encoder -> embedding -> InfoNCE), and of its consumer, the TCN mixer of the
+ * style-transfer stage (embeddings -> FiLM generator -> dilated residual Conv1d stack on the stems; inference).
  *
  * The reference is 100 % Python and has no FFI; the drop-in boundary is its Python call
  * contract.  Each entry point below names the reference code whose
@@ -451,6 +452,55 @@ int mst_infonce_forward(const float* emb, const int64_t* labels, int N, int D, i
  * scale: dev [1] (the upstream gradient, e.g. 1/#valid anchors) or NULL for 1.  Same workspace size as forward. */
 int mst_infonce_backward(const float* emb, const int64_t* labels, int N, int D, int row0, int rows,
                          float temperature, const float* scale, float* grad, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Stage C: TCN mixer (eval) -- the style-transfer stage that consumes the embeddings.
+ * Replaces: TCNMixer.forward src/tcn_mixer.py:285-321 (input 1x1 conv, num_blocks residual blocks with dilation
+ * 2^i, output 1x1 conv + x), ResidualBlock.forward :82-90, FiLMResidualBlock.forward :119-145, CausalConv1d :16-36,
+ * NonCausalConv1d :39-57, TCNFiLMGenerator.forward :186-216, as driven by
+ * inference/inference_e2e_style_transfer.py:124-177.  BatchNorm1d uses running statistics, Dropout is identity,
+ * LeakyReLU slope 0.2.  Exact fp32 (fp32 MFMA).  Padding is zeros of each layer's own input.
+ * Geometry: in_channels == 8, hidden_channels <= 128 (padded inside the handle to a multiple of 16 with zero
+ * weights: exact), kernel_size <= 15 (odd unless causal), num_blocks <= 16.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct mst_tcn mst_tcn;           /* mixer          */
+typedef struct mst_tcn_film mst_tcn_film; /* FiLM generator */
+typedef struct mst_tcn_config {
+  int32_t in_channels, hidden_channels, num_blocks, kernel_size;
+  int32_t causal;   /* 0: symmetric padding ((K-1)*d)/2; 1: (K-1)*d zeros on the left only                     */
+  int32_t use_film; /* 0: ResidualBlock (activation after the residual sum); 1: FiLMResidualBlock (before it)  */
+  float bn_eps;
+} mst_tcn_config;
+/* host fp32, the state_dict tensors; per-block tensors stacked over (block, layer = conv1/norm1, conv2/norm2). */
+typedef struct mst_tcn_weights {
+  const float *input_w, *input_b;   /* input_conv  [H][8][1], [H]                                   */
+  const float *conv_w, *conv_b;     /* blocks.{i}.conv{1,2}.conv  [nb][2][H][H][K], [nb][2][H]      */
+  const float *bn_w, *bn_b, *bn_mean, *bn_var; /* blocks.{i}.norm{1,2}  [nb][2][H] each             */
+  const float *output_w, *output_b; /* output_conv [8][H][1], [8]                                   */
+} mst_tcn_weights;
+/* optional: the hidden state after chosen blocks in the reference's layout, for the tests */
+typedef struct mst_tcn_taps {
+  int32_t n;        /* 0..4 */
+  int32_t block[4]; /* block index whose output is copied                    */
+  float* h[4];      /* dev [B][H][T] each                                    */
+} mst_tcn_taps;
+typedef struct mst_tcn_film_weights { const float *mlp0_w, *mlp0_b, *mlp3_w, *mlp3_b, *mlp6_w, *mlp6_b; } mst_tcn_film_weights;
+
+int mst_tcn_create(mst_tcn** out, const mst_tcn_config* cfg, const mst_tcn_weights* w);
+void mst_tcn_destroy(mst_tcn* tcn);
+/* 0 (and mst_last_error) when the shape is refused: H_padded * T must stay below 2^31 per clip, B <= 65535. */
+size_t mst_tcn_workspace_bytes(const mst_tcn* tcn, int B, long long T);
+/* x, y: dev [B][8][T] fp32 (y may not alias x).  film: dev [B][num_blocks][4][H] = gamma1, beta1, gamma2, beta2 per
+ * block (what mst_tcn_film_forward writes); required iff use_film.  taps may be NULL.                            */
+int mst_tcn_forward(const mst_tcn* tcn, const float* x, const float* film, int B, long long T, float* y,
+                    const mst_tcn_taps* taps, void* workspace, size_t workspace_bytes, void* stream);
+/* Linear(embed_dim, 512) - LeakyReLU - Linear(512, 512) - LeakyReLU - Linear(512, num_blocks*4*hidden); embed_dim % 4 == 0. */
+int mst_tcn_film_create(mst_tcn_film** out, int embed_dim, int num_blocks, int hidden, const mst_tcn_film_weights* w);
+void mst_tcn_film_destroy(mst_tcn_film* gen);
+size_t mst_tcn_film_workspace_bytes(const mst_tcn_film* gen, int B);
+/* emb: dev [B][embed_dim] (input and target embedding concatenated); film: dev [B][num_blocks][4][hidden]. */
+int mst_tcn_film_forward(const mst_tcn_film* gen, const float* emb, int B, float* film, void* workspace,
                          size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus

@@ -86,6 +86,24 @@ class FilmPtrs(C.Structure):   # mst_film_weights / mst_film_grads
     _fields_ = [(k, C.c_void_p) for k in ("mlp0_w", "mlp0_b", "mlp3_w", "mlp3_b", "head_w", "head_b")]
 
 
+class TcnConfig(C.Structure):
+    _fields_ = [("in_channels", C.c_int32), ("hidden_channels", C.c_int32), ("num_blocks", C.c_int32),
+                ("kernel_size", C.c_int32), ("causal", C.c_int32), ("use_film", C.c_int32), ("bn_eps", C.c_float)]
+
+
+class TcnWeights(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("input_w", "input_b", "conv_w", "conv_b", "bn_w", "bn_b", "bn_mean", "bn_var",
+                                          "output_w", "output_b")]
+
+
+class TcnTaps(C.Structure):
+    _fields_ = [("n", C.c_int32), ("block", C.c_int32 * 4), ("h", C.c_void_p * 4)]
+
+
+class TcnFilmWeights(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("mlp0_w", "mlp0_b", "mlp3_w", "mlp3_b", "mlp6_w", "mlp6_b")]
+
+
 SYMBOLS = {
     "mst_version": (C.c_int, []),
     "mst_last_error": (C.c_char_p, []),
@@ -168,6 +186,15 @@ SYMBOLS = {
                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mst_infonce_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mst_tcn_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(TcnConfig), C.POINTER(TcnWeights)]),
+    "mst_tcn_destroy": (None, [C.c_void_p]),
+    "mst_tcn_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_longlong]),
+    "mst_tcn_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.POINTER(TcnTaps),
+                                  C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mst_tcn_film_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.POINTER(TcnFilmWeights)]),
+    "mst_tcn_film_destroy": (None, [C.c_void_p]),
+    "mst_tcn_film_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "mst_tcn_film_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 _lib = None
