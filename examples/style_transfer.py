@@ -8,6 +8,7 @@ inference/inference_e2e_style_transfer.py does once the stems are separated:
 
     python examples/style_transfer.py                       # two seeded synthetic clips, seeded weights
     python examples/style_transfer.py --tcn_checkpoint ckpt.pt --encoder_checkpoint enc.pt --seconds 10
+    python examples/style_transfer.py --cycle               # + the cycle-consistency distance of the trainer (no gradient step)
 
 --tcn_checkpoint is the reference's format (train_style_transfer.py): a dict with `tcn_state_dict`,
 `film_generator_state_dict` and optionally `hidden_channels`, `num_blocks`, `kernel_size`, `causal` (defaults 16, 8, 5,
@@ -21,6 +22,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from mst_amd.loss import MultiResolutionSTFTLoss  # noqa: E402
 from mst_amd.mixing_utils import STEMS, deferred_features  # noqa: E402
 from mst_amd.model import MixingStyleEncoder  # noqa: E402
 from mst_amd.synth import synth_batch  # noqa: E402
@@ -45,6 +47,8 @@ def main(argv=None):
     ap.add_argument("--tcn_checkpoint", default=None)
     ap.add_argument("--encoder_checkpoint", default=None, help="state_dict of MixingStyleEncoder (reference format)")
     ap.add_argument("--backend", choices=["hip", "torch"], default="hip")
+    ap.add_argument("--cycle", action="store_true",
+                    help="also send the processed stems back (style of the input) and print the MR-STFT distance to the input stems")
     a = ap.parse_args(argv)
     device = torch.device("cuda")
     torch.manual_seed(a.seed)
@@ -76,6 +80,15 @@ def main(argv=None):
     print(f"TCN: {nb} blocks, {H} channels, receptive field {tcn.receptive_field} samples, backend {a.backend}")
     print(f"processed mixture {tuple(out['processed_mixture'].shape)}, max |y - x| = {float((y - x[0]).abs().max()):.4f}")
     print(f"cosine distance to the target: input {distance(e_in, e_tgt):.4f} -> processed {distance(e_out, e_tgt):.4f}")
+    if a.cycle:   # train_style_transfer.py:228-239: output -> reconstructed input, MultiResolutionSTFTLoss(reconstructed, input)
+        back = apply_style_transfer(tcn, gen, {s: y[2 * i:2 * i + 2] for i, s in enumerate(STEMS)}, e_in, e_out, device)
+        rec = torch.cat([back["processed_stems"][s] for s in STEMS], 0).to(device)
+        crit = MultiResolutionSTFTLoss(backend=a.backend)
+        with torch.no_grad():
+            cyc, comp = float(crit(rec, x[0].to(device))), crit.components(rec, x[0].to(device)).cpu()
+        out["cycle_loss"] = cyc
+        print(f"cycle MR-STFT distance input -> target style -> input style: {cyc:.4f}  (per resolution sc / log: "
+              + ", ".join(f"{n}: {c[0]:.3f} / {c[1]:.3f}" for n, c in zip(crit.fft_sizes, comp.tolist())) + ")")
     return out
 
 

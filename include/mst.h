@@ -455,6 +455,27 @@ int mst_infonce_backward(const float* emb, const int64_t* labels, int N, int D, 
                          size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Stage C loss: multi-resolution STFT loss of the style-transfer trainer, forward and the gradient to x.
+ * Replaces: MultiResolutionSTFTLoss.forward src/loss.py:332-448 (torch.stft center=True / reflect, periodic Hann,
+ * magnitudes, spectral convergence + mean |log(xm + 1e-5) - log(ym + 1e-5)| per resolution, mean over resolutions).
+ * x, y: dev fp32 [rows][T], rows = B * C.  fft[], hop[]: host, n_res entries; fft in {512, 1024, 2048} (window length
+ * = fft), hop in {fft/8, fft/4, fft/2}, T > max(fft) / 2.  windows: host array of n_res DEVICE pointers, windows[r] =
+ * fp32 [fft[r]] (built by the caller on the host; never re-derived on the device).
+ * out: dev fp32 [1 + 4 n_res] = { loss, (sc, log) x n_res unweighted, (||ym - xm||_F, ||ym||_F) x n_res }; the backward
+ * pass takes it back as fwd_out.  Bit-reproducible (no floating-point atomics), stream-ordered, no host sync.
+ * ------------------------------------------------------------------------------------------ */
+size_t mst_mrstft_workspace_bytes(int n_res, const int* fft, const int* hop, int rows, int T);
+int mst_mrstft_forward(const float* x, const float* y, int rows, int T, int n_res, const int* fft, const int* hop,
+                       const float* const* windows, float sc_weight, float log_weight, float* out, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* grad_x: dev [rows][T] = grad_scale * d loss / d x (every element written).  grad_scale: dev [1] (the upstream
+ * gradient) or NULL for 1.  Recomputes the frames: needs x, y and the forward's out, not its workspace contents.  */
+int mst_mrstft_backward(const float* x, const float* y, int rows, int T, int n_res, const int* fft, const int* hop,
+                        const float* const* windows, float sc_weight, float log_weight, const float* fwd_out,
+                        const float* grad_scale, float* grad_x, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Stage C: TCN mixer (eval) -- the style-transfer stage that consumes the embeddings.
  * Replaces: TCNMixer.forward src/tcn_mixer.py:285-321 (input 1x1 conv, num_blocks residual blocks with dilation
  * 2^i, output 1x1 conv + x), ResidualBlock.forward :82-90, FiLMResidualBlock.forward :119-145, CausalConv1d :16-36,

@@ -1,0 +1,461 @@
+// Multi-resolution STFT loss (the cycle-consistency loss of the style-transfer trainer), forward and the gradient to the
+// first argument.  Replaces MultiResolutionSTFTLoss.forward src/loss.py:332-448 and what autograd derives from it:
+//   per resolution  X = stft(x), Y = stft(y)  (center=True, reflect padding n/2, periodic Hann, one-sided, 1 + T/hop frames),
+//   xm = |X|, ym = |Y|,  sc = ||ym - xm||_F / (||ym||_F + 1e-8),  lg = mean |log(xm + 1e-5) - log(ym + 1e-5)|,
+//   loss = mean over resolutions of (sc_weight sc + log_weight lg).
+// One wave transforms a PAIR of consecutive frames of one signal as re/im of one complex FFT (fft_wave.h) and splits the
+// two spectra apart.  x and y go through the SAME instruction sequence in separate transforms, so x == y gives xm == ym bit
+// for bit (loss and gradient exactly 0, as the reference) -- packing x and y into one transform would not.
+// n_fft = 2048 is one decimation-in-time step over two 1024-point wave FFTs (even / odd samples), as stage A does.
+// The three sums of a resolution are added up in double per lane, per wave, per workgroup and then across workgroups through
+// the order-independent integer accumulators (DetAcc): the loss is bit-reproducible.
+// Backward recomputes the frames (storing the complex spectra of 64 x 441 000 samples at three resolutions would be
+// 2-4x the audio per resolution, written and read again): per bin the real cotangent on xm is
+//   c = -sc_weight (ym - xm) / (||ym - xm|| (||ym|| + 1e-8)) + log_weight sign(log(xm + 1e-5) - log(ym + 1e-5)) / (Nbins (xm + 1e-5)),
+// G = c X / |X| (0 where X == 0), and the adjoint STFT of G: the Hermitian completions of the two frames' G ride as re / im of
+// ONE inverse transform, the result is windowed and overlap-added.  A workgroup owns a contiguous span of hop-sized chunks of
+// the PADDED signal and computes every frame that touches it (n/hop - 1 frames of halo per 64 chunks); the frames are added
+// into an LDS ring in a fixed order (no floating-point atomics), finished chunks are flushed.  The two n/2-sample borders of
+// the padding go to a small buffer and are folded back into the clip by a second kernel (adjoint of the reflection).
+#include "common.h"
+#include <algorithm>
+
+#include "fft_wave.h"
+
+namespace {
+using namespace mstfft;
+
+constexpr int kWaves = 4, kThreads = kWaves * 64, kRound = 2 * kWaves;   // frames per round of a workgroup
+constexpr int kChunksPerBlock = 64;
+constexpr int kFwdMaxBlocks = 2048;   // DetAcc takes up to 2^14 contributions
+constexpr int kMaxRes = 16;
+constexpr int kBorder = 1024;         // floats per border and row (n_fft / 2 at most)
+
+template <int N>
+struct Geo {
+  static constexpr int NC = N == 2048 ? 1024 : N;   // complex length of the wave FFT
+  static constexpr int NF = N / NC, NCR = NC / 64, REGS = N / 64, SCR = N + N / 8, TW = FftPlan<NC>::TW;
+  static constexpr int TWD = N == 2048 ? 1024 : 0, NB = N / 128 + 1;
+  static constexpr size_t kLds = (size_t)(TW + TWD) * 8 + (size_t)N * 4 + (size_t)kWaves * SCR * 8;
+};
+
+// element a lane holds in register r before the first pass / after the last pass
+template <int N>
+__device__ __forceinline__ int in_idx(int r, int lane) {
+  if constexpr (N == 2048) return 2 * (lane + 64 * in_q<1024>(r & 15)) + (r >> 4);
+  else return lane + 64 * in_q<N>(r);
+}
+template <int N>
+__device__ __forceinline__ int out_idx(int r, int lane) {
+  constexpr int NC = Geo<N>::NC, RL = FftPlan<NC>::RL, NBFL = NC / RL / 64;
+  const int rr = r % (NC / 64);
+  return lane + 64 * ((rr / RL) + (rr % RL) * NBFL) + (N == 2048 ? 1024 * (r / (NC / 64)) : 0);
+}
+
+__device__ __forceinline__ void wsync() {   // the wave's LDS traffic before / after this point stays there
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+template <int N>
+struct Lds {
+  float2* tw;    // FftPlan<NC> twiddles
+  float2* twd;   // N == 2048: W_2048^k, k < 1024
+  float* win;    // [N]
+  float2* scr;   // this wave's scratch [SCR]
+  float* acc;    // backward: ring of chunks
+  __device__ Lds(unsigned char* smem, int wave) {
+    using G = Geo<N>;
+    tw = reinterpret_cast<float2*>(smem);
+    twd = tw + G::TW;
+    float2* s0 = twd + G::TWD;
+    scr = s0 + wave * G::SCR;
+    win = reinterpret_cast<float*>(s0 + kWaves * G::SCR);
+    acc = win + N;
+  }
+  __device__ void fill(const float* window, int tid) {
+    fill_twiddles<Geo<N>::NC>(tw, tid, kThreads);
+    if constexpr (N == 2048)
+      for (int k = tid; k < 1024; k += kThreads) {
+        double sn, cs;
+        sincospi(-2.0 * (double)k / 2048.0, &sn, &cs);
+        twd[k] = make_float2((float)cs, (float)sn);
+      }
+    for (int i = tid; i < N; i += kThreads) win[i] = window[i];
+  }
+};
+
+template <int N>
+__device__ __forceinline__ void wave_fft(float2 (&v)[Geo<N>::NF][Geo<N>::NCR], const Lds<N>& l, int lane) {
+  using G = Geo<N>;
+  wsync();
+  FftPlan<G::NC>::template run<G::NF>(v, l.scr, l.tw, lane);
+  if constexpr (N == 2048) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const float2 t = cmul(v[1][i], l.twd[out_idx<N>(i, lane)]), e = v[0][i];
+      v[0][i] = cadd(e, t);
+      v[1][i] = csub(e, t);
+    }
+  }
+  wsync();
+}
+
+__device__ __forceinline__ int reflect(int t, int T) { return t < 0 ? -t : (t >= T ? 2 * (T - 1) - t : t); }
+
+// windowed frames starting at sample `start` (re) and `start + hop` (im, zero without a second frame) of one row
+template <int N>
+__device__ __forceinline__ void load_pair(const float* __restrict__ s, int T, int start, int hop, bool hasB, const Lds<N>& l,
+                                          float2 (&v)[Geo<N>::NF][Geo<N>::NCR], int lane) {
+  using G = Geo<N>;
+  const bool inner = hasB && start >= 0 && start + hop + N <= T;   // wave-uniform
+#pragma unroll
+  for (int r = 0; r < G::REGS; ++r) {
+    const int n = in_idx<N>(r, lane);
+    const float w = l.win[n];
+    const int ta = inner ? start + n : reflect(start + n, T);
+    const int tb = !hasB ? ta : (inner ? start + hop + n : reflect(start + hop + n, T));   // (no read past the row without a frame)
+    const float a = s[ta], b = hasB ? s[tb] : 0.f;
+    v[r / G::NCR][r % G::NCR] = make_float2(a * w, b * w);
+  }
+}
+
+// Z = FFT(a + i b) in registers -> the one-sided spectra of a and b; bin k = lane + 64 j in slot j, Nyquist in the last slot of lane 0
+template <int N>
+__device__ __forceinline__ void split_pair(const float2 (&v)[Geo<N>::NF][Geo<N>::NCR], const Lds<N>& l, int lane,
+                                           float2 (&SA)[Geo<N>::NB], float2 (&SB)[Geo<N>::NB]) {
+  using G = Geo<N>;
+#pragma unroll
+  for (int r = 0; r < G::REGS; ++r) l.scr[pad8(out_idx<N>(r, lane))] = v[r / G::NCR][r % G::NCR];
+  wsync();
+#pragma unroll
+  for (int j = 0; j < G::NB - 1; ++j) {
+    const int k = lane + 64 * j;
+    const float2 a = l.scr[pad8(k)], b = l.scr[pad8((N - k) & (N - 1))];
+    SA[j] = make_float2(0.5f * (a.x + b.x), 0.5f * (a.y - b.y));
+    SB[j] = make_float2(0.5f * (a.y + b.y), 0.5f * (b.x - a.x));
+  }
+  const float2 q = l.scr[pad8(N / 2)];
+  SA[G::NB - 1] = make_float2(lane == 0 ? q.x : 0.f, 0.f);
+  SB[G::NB - 1] = make_float2(lane == 0 ? q.y : 0.f, 0.f);
+  wsync();
+}
+
+__device__ __forceinline__ float cabs2(float2 z) { return sqrtf(fmaf(z.x, z.x, z.y * z.y)); }
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+struct FwdParams {
+  const float* x;
+  const float* y;
+  const float* window;
+  mst::DetAcc* acc;   // [3]: sum (ym - xm)^2, sum ym^2, sum |log(xm + 1e-5) - log(ym + 1e-5)|
+  int rows, T, hop, F, pairs_per_row;
+};
+
+template <int N>
+__global__ __launch_bounds__(kThreads) void mrstft_fwd_kernel(const FwdParams p) {
+  using G = Geo<N>;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ double red[kWaves][3];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  Lds<N> l(smem, wave);
+  l.fill(p.window, tid);
+  __syncthreads();
+  double d2 = 0.0, y2 = 0.0, la = 0.0;
+  const int items = p.rows * p.pairs_per_row;
+  for (int it = blockIdx.x * kWaves + wave; it < items; it += gridDim.x * kWaves) {
+    const int row = it / p.pairs_per_row, f = 2 * (it % p.pairs_per_row);
+    const bool hasB = f + 1 < p.F;
+    const int start = f * p.hop - N / 2;
+    float2 v[G::NF][G::NCR], SA[G::NB], SB[G::NB];
+    float xa[G::NB], xb[G::NB];
+    load_pair<N>(p.x + (size_t)row * p.T, p.T, start, p.hop, hasB, l, v, lane);
+    wave_fft<N>(v, l, lane);
+    split_pair<N>(v, l, lane, SA, SB);
+#pragma unroll
+    for (int j = 0; j < G::NB; ++j) xa[j] = cabs2(SA[j]), xb[j] = cabs2(SB[j]);
+    load_pair<N>(p.y + (size_t)row * p.T, p.T, start, p.hop, hasB, l, v, lane);
+    wave_fft<N>(v, l, lane);
+    split_pair<N>(v, l, lane, SA, SB);
+#pragma unroll
+    for (int j = 0; j < G::NB; ++j) {
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        if (e && !hasB) continue;   // no second frame: its "spectrum" is the rounding residue of the split, not zero
+        const float xm = e ? xb[j] : xa[j], ym = cabs2(e ? SB[j] : SA[j]);
+        const float d = ym - xm, lg = fabsf(logf(xm + 1e-5f) - logf(ym + 1e-5f));
+        d2 += (double)d * (double)d;
+        y2 += (double)ym * (double)ym;
+        la += (double)lg;
+      }
+    }
+  }
+  d2 = wave_sum_d(d2), y2 = wave_sum_d(y2), la = wave_sum_d(la);
+  if (lane == 0) red[wave][0] = d2, red[wave][1] = y2, red[wave][2] = la;
+  __syncthreads();
+  if (tid < 3) {
+    double s = 0.0;
+    for (int w = 0; w < kWaves; ++w) s += red[w][tid];
+    mst::det_add(p.acc + tid, s);
+  }
+}
+
+// out: [0] loss, [1 + 2 r + {0, 1}] (sc, lg) of resolution r, [1 + 2 n + 2 r + {0, 1}] (||ym - xm||, ||ym||) for the backward pass
+struct BinCounts {
+  double v[kMaxRes];
+};
+__global__ void mrstft_finish_kernel(const mst::DetAcc* acc, int n_res, const BinCounts nbins, float sc_w, float log_w, float* out) {
+  if (threadIdx.x != 0) return;
+  double total = 0.0;
+  for (int r = 0; r < n_res; ++r) {
+    const double dn = sqrt(mst::det_get(acc[3 * r])), yn = sqrt(mst::det_get(acc[3 * r + 1]));
+    const double sc = dn / (yn + 1e-8), lg = mst::det_get(acc[3 * r + 2]) / nbins.v[r];
+    out[1 + 2 * r] = (float)sc;
+    out[2 + 2 * r] = (float)lg;
+    out[1 + 2 * n_res + 2 * r] = (float)dn;
+    out[2 + 2 * n_res + 2 * r] = (float)yn;
+    total += (double)sc_w * sc + (double)log_w * lg;
+  }
+  out[0] = (float)(total / n_res);
+}
+
+struct BwdParams {
+  const float* x;
+  const float* y;
+  const float* window;
+  const float* norms;   // dev [2]: ||ym - xm||, ||ym|| of this resolution (from the forward pass)
+  float* grad;          // [rows][T]
+  float* border;        // [rows][2][kBorder]: cotangent of the left padding (sample -1 - j) and of the right (sample T + j)
+  int rows, T, hop, lh, R, F, nchunks, blocks_per_row, accumulate;
+  float sc_w, log_w_over_n;
+};
+
+template <int N>
+__global__ __launch_bounds__(kThreads) void mrstft_bwd_kernel(const BwdParams p) {
+  using G = Geo<N>;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  Lds<N> l(smem, wave);
+  l.fill(p.window, tid);
+  const int hop = p.hop, lh = p.lh, R = p.R, nslot = kRound + R - 1;
+  for (int i = tid; i < nslot * hop; i += kThreads) l.acc[i] = 0.f;
+  const int row = blockIdx.x / p.blocks_per_row, blk = blockIdx.x % p.blocks_per_row;
+  const int c0 = blk * kChunksPerBlock, c1 = min(c0 + kChunksPerBlock, p.nchunks);
+  const int fa = max(0, c0 - R + 1), fb = min(p.F - 1, c1 - 1);
+  const float dn = p.norms[0], yn = p.norms[1];
+  const float ksc = dn > 0.f ? p.sc_w / (dn * (yn + 1e-8f)) : 0.f, klog = p.log_w_over_n;
+  const float* xr = p.x + (size_t)row * p.T;
+  const float* yr = p.y + (size_t)row * p.T;
+  float* gr = p.grad + (size_t)row * p.T;
+  float* bl = p.border + (size_t)row * 2 * kBorder;
+  __syncthreads();
+  for (int fr0 = fa; fr0 < c1; fr0 += kRound) {
+    const int gA = fr0 + 2 * wave;
+    const bool hasA = gA <= fb, hasB = gA + 1 <= fb;
+    float2 v[G::NF][G::NCR];
+    if (hasA) {   // wave-uniform
+      const int start = gA * hop - N / 2;
+      float2 XA[G::NB], XB[G::NB], SA[G::NB], SB[G::NB];
+      load_pair<N>(xr, p.T, start, hop, hasB, l, v, lane);
+      wave_fft<N>(v, l, lane);
+      split_pair<N>(v, l, lane, XA, XB);
+      load_pair<N>(yr, p.T, start, hop, hasB, l, v, lane);
+      wave_fft<N>(v, l, lane);
+      split_pair<N>(v, l, lane, SA, SB);
+      // cotangent of the two spectra, packed: conj(H), H = herm(G_A) + i herm(G_B)
+#pragma unroll
+      for (int j = 0; j < G::NB; ++j) {
+        float2 g[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          const float2 X = e ? XB[j] : XA[j];
+          const float xm = cabs2(X), ym = cabs2(e ? SB[j] : SA[j]);
+          const float d = ym - xm, lg = logf(xm + 1e-5f) - logf(ym + 1e-5f);
+          const float sg = lg > 0.f ? 1.f : (lg < 0.f ? -1.f : 0.f);
+          const float c = -ksc * d + klog * sg / (xm + 1e-5f);
+          g[e] = (xm > 0.f && !(e && !hasB)) ? make_float2(c * (X.x / xm), c * (X.y / xm)) : make_float2(0.f, 0.f);   // (no frame: no cotangent)
+        }
+        const float ar = g[0].x, ai = g[0].y, br = g[1].x, bi = g[1].y;
+        if (j == G::NB - 1) {
+          if (lane == 0) l.scr[pad8(N / 2)] = make_float2(ar, -br);
+        } else {
+          const int k = lane + 64 * j;
+          if (k == 0) {
+            l.scr[pad8(0)] = make_float2(ar, -br);
+          } else {
+            l.scr[pad8(k)] = make_float2(0.5f * (ar - bi), -0.5f * (ai + br));
+            l.scr[pad8(N - k)] = make_float2(0.5f * (ar + bi), 0.5f * (ai - br));
+          }
+        }
+      }
+      wsync();
+#pragma unroll
+      for (int r = 0; r < G::REGS; ++r) v[r / G::NCR][r % G::NCR] = l.scr[pad8(in_idx<N>(r, lane))];
+      wave_fft<N>(v, l, lane);   // = g_A[n] - i g_B[n]
+    }
+    // overlap-add in a fixed order: in phase ph the frames fr0 + ph (mod R) -- R frames apart, they do not overlap
+    for (int ph = 0; ph < R; ++ph) {
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const int g = gA + e;
+        if ((e ? hasB : hasA) && ((g - fr0) & (R - 1)) == ph) {   // wave-uniform
+#pragma unroll
+          for (int r = 0; r < G::REGS; ++r) {
+            const int nb = out_idx<N>(r, 0);   // lane + 64 q stays inside one chunk: hop is a multiple of 64
+            const int slot = (g + (nb >> lh)) % nslot;
+            const float2 z = v[r / G::NCR][r % G::NCR];
+            l.acc[slot * hop + (nb & (hop - 1)) + lane] += l.win[nb + lane] * (e ? -z.y : z.x);
+          }
+        }
+      }
+      __syncthreads();
+    }
+    // chunks [fr0, fr0 + kRound) are complete: no later frame reaches them
+    const int nfl = min(fr0 + kRound, c1) - fr0;
+    for (int i = tid; i < nfl * hop; i += kThreads) {
+      const int c = fr0 + (i >> lh), off = i & (hop - 1);
+      float* a = l.acc + (c % nslot) * hop + off;
+      const float val = *a;
+      *a = 0.f;
+      const int pp = c * hop + off;
+      if (c >= c0 && pp < p.T + N) {
+        const int t = pp - N / 2;
+        if (t < 0) bl[-t - 1] = val;
+        else if (t >= p.T) bl[kBorder + t - p.T] = val;
+        else gr[t] = p.accumulate ? gr[t] + val : val;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// adjoint of the reflect padding: sample -1 - j folds onto 1 + j, sample T + j onto T - 2 - j
+__global__ __launch_bounds__(256) void mrstft_fold_kernel(float* grad, const float* border, int T, int half) {
+  float* g = grad + (size_t)blockIdx.x * T;
+  const float* b = border + (size_t)blockIdx.x * 2 * kBorder;
+  for (int j = threadIdx.x; j < half; j += 256) g[1 + j] += b[j];
+  __syncthreads();
+  for (int j = threadIdx.x; j < half; j += 256) g[T - 2 - j] += b[kBorder + j];
+}
+
+__global__ __launch_bounds__(256) void mrstft_scale_kernel(float* grad, size_t n, const float* scale, float inv_res) {
+  const float s = scale ? *scale : 1.0f;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) grad[i] = s * (grad[i] * inv_res);
+}
+
+int log2_exact(int v) {
+  int l = 0;
+  while ((1 << l) < v) ++l;
+  return l;
+}
+
+template <int N>
+hipError_t launch_fwd(const FwdParams& p, int grid, hipStream_t st) {
+  const size_t lds = Geo<N>::kLds;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrstft_fwd_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((mrstft_fwd_kernel<N>), dim3(grid), dim3(kThreads), lds, st, p);
+  return hipGetLastError();
+}
+template <int N>
+hipError_t launch_bwd(const BwdParams& p, int grid, hipStream_t st) {
+  const size_t lds = Geo<N>::kLds + (size_t)(kRound + p.R - 1) * p.hop * sizeof(float);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrstft_bwd_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((mrstft_bwd_kernel<N>), dim3(grid), dim3(kThreads), lds, st, p);
+  return hipGetLastError();
+}
+
+size_t acc_bytes(int n_res) { return mst::align_up((size_t)3 * n_res * sizeof(mst::DetAcc), 256); }
+
+int check_args(const char* who, int rows, int T, int n_res, const int* fft, const int* hop) {
+  MST_REQUIRE(fft && hop, "%s: NULL argument", who);
+  MST_REQUIRE(n_res >= 1 && n_res <= kMaxRes, "%s: n_res=%d outside 1..%d", who, n_res, kMaxRes);
+  MST_REQUIRE(rows > 0 && rows <= (1 << 20) && T > 0 && T < (1 << 30), "%s: bad sizes rows=%d T=%d", who, rows, T);
+  for (int r = 0; r < n_res; ++r) {
+    MST_REQUIRE(fft[r] == 512 || fft[r] == 1024 || fft[r] == 2048, "%s: n_fft=%d is not 512, 1024 or 2048", who, fft[r]);
+    MST_REQUIRE(hop[r] == fft[r] / 8 || hop[r] == fft[r] / 4 || hop[r] == fft[r] / 2, "%s: hop=%d is not n_fft/8, /4 or /2 (n_fft=%d)",
+                who, hop[r], fft[r]);
+    MST_REQUIRE(T > fft[r] / 2, "%s: T=%d needs more than n_fft/2 = %d samples (reflect padding)", who, T, fft[r] / 2);
+  }
+  return MST_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mst_mrstft_workspace_bytes(int n_res, const int* fft, const int* hop, int rows, int T) {
+  if (n_res <= 0 || rows <= 0 || T <= 0 || !fft || !hop) return 0;
+  return acc_bytes(n_res) + mst::align_up((size_t)rows * 2 * kBorder * sizeof(float), 256);
+}
+
+int mst_mrstft_forward(const float* x, const float* y, int rows, int T, int n_res, const int* fft, const int* hop,
+                       const float* const* windows, float sc_weight, float log_weight, float* out, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  MST_REQUIRE(x && y && windows && out, "mst_mrstft_forward: NULL argument");
+  if (int rc = check_args("mst_mrstft_forward", rows, T, n_res, fft, hop)) return rc;
+  const size_t need = mst_mrstft_workspace_bytes(n_res, fft, hop, rows, T);
+  if (!workspace || workspace_bytes < need)
+    return mst::fail(MST_ENOMEM, "mst_mrstft_forward: workspace %zu B < required %zu B", workspace_bytes, need);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  mst::DetAcc* acc = reinterpret_cast<mst::DetAcc*>(workspace);
+  MST_HIP_CHECK(hipMemsetAsync(acc, 0, (size_t)3 * n_res * sizeof(mst::DetAcc), st));
+  BinCounts nb;
+  for (int r = 0; r < kMaxRes; ++r) nb.v[r] = 1.0;
+  for (int r = 0; r < n_res; ++r) {
+    MST_REQUIRE(windows[r], "mst_mrstft_forward: NULL window table %d", r);
+    FwdParams p;
+    p.x = x, p.y = y, p.window = windows[r], p.acc = acc + 3 * r;
+    p.rows = rows, p.T = T, p.hop = hop[r], p.F = 1 + T / hop[r], p.pairs_per_row = (p.F + 1) / 2;
+    nb.v[r] = (double)rows * p.F * (fft[r] / 2 + 1);
+    const long long items = (long long)rows * p.pairs_per_row;
+    MST_REQUIRE(items < (1LL << 31), "mst_mrstft_forward: %lld frame pairs", items);
+    const int grid = (int)std::min<long long>((items + kWaves - 1) / kWaves, kFwdMaxBlocks);
+    MST_HIP_CHECK(fft[r] == 512 ? launch_fwd<512>(p, grid, st) : fft[r] == 1024 ? launch_fwd<1024>(p, grid, st) : launch_fwd<2048>(p, grid, st));
+  }
+  hipLaunchKernelGGL(mrstft_finish_kernel, dim3(1), dim3(64), 0, st, acc, n_res, nb, sc_weight, log_weight, out);
+  MST_HIP_CHECK(hipGetLastError());
+  return MST_OK;
+}
+
+int mst_mrstft_backward(const float* x, const float* y, int rows, int T, int n_res, const int* fft, const int* hop,
+                        const float* const* windows, float sc_weight, float log_weight, const float* fwd_out,
+                        const float* grad_scale, float* grad_x, void* workspace, size_t workspace_bytes, void* stream) {
+  MST_REQUIRE(x && y && windows && fwd_out && grad_x, "mst_mrstft_backward: NULL argument");
+  if (int rc = check_args("mst_mrstft_backward", rows, T, n_res, fft, hop)) return rc;
+  const size_t need = mst_mrstft_workspace_bytes(n_res, fft, hop, rows, T);
+  if (!workspace || workspace_bytes < need)
+    return mst::fail(MST_ENOMEM, "mst_mrstft_backward: workspace %zu B < required %zu B", workspace_bytes, need);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  float* border = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + acc_bytes(n_res));
+  for (int r = 0; r < n_res; ++r) {
+    MST_REQUIRE(windows[r], "mst_mrstft_backward: NULL window table %d", r);
+    BwdParams p;
+    p.x = x, p.y = y, p.window = windows[r], p.norms = fwd_out + 1 + 2 * n_res + 2 * r, p.grad = grad_x, p.border = border;
+    p.rows = rows, p.T = T, p.hop = hop[r], p.lh = log2_exact(hop[r]), p.R = fft[r] / hop[r], p.F = 1 + T / hop[r];
+    p.nchunks = (int)(((long long)T + fft[r] + hop[r] - 1) / hop[r]);
+    p.blocks_per_row = (p.nchunks + kChunksPerBlock - 1) / kChunksPerBlock;
+    p.accumulate = r > 0;
+    p.sc_w = sc_weight;
+    p.log_w_over_n = (float)((double)log_weight / ((double)rows * p.F * (fft[r] / 2 + 1)));
+    const long long grid = (long long)rows * p.blocks_per_row;
+    MST_REQUIRE(grid < (1LL << 31), "mst_mrstft_backward: %lld workgroups", grid);
+    MST_HIP_CHECK(fft[r] == 512 ? launch_bwd<512>(p, (int)grid, st) : fft[r] == 1024 ? launch_bwd<1024>(p, (int)grid, st) : launch_bwd<2048>(p, (int)grid, st));
+    hipLaunchKernelGGL(mrstft_fold_kernel, dim3(rows), dim3(256), 0, st, grad_x, border, T, fft[r] / 2);
+  }
+  const size_t n = (size_t)rows * T;
+  hipLaunchKernelGGL(mrstft_scale_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st, grad_x, n, grad_scale,
+                     1.0f / (float)n_res);
+  MST_HIP_CHECK(hipGetLastError());
+  return MST_OK;
+}
+
+}  // extern "C"

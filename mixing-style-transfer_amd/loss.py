@@ -2,7 +2,12 @@
 sharded: with torch.distributed initialised, embeddings and labels cross RCCL/xGMI in ONE packed all-gather and every
 rank evaluates the (tiny) loss on the whole gathered batch -- no other collective in forward or backward
 (SURVEY.md section 8e).  On CUDA/HIP tensors forward and backward run in libmst.so (`mst_infonce_forward/backward`);
-CPU tensors (the gloo tests of the sharding logic) take the same formulas in torch ops."""
+CPU tensors (the gloo tests of the sharding logic) take the same formulas in torch ops.
+
+MultiResolutionSTFTLoss is the cycle-consistency loss of the style-transfer trainer (src/loss.py:332-448): forward and the
+gradient to the reconstructed audio in libmst.so (`mst_mrstft_forward/backward`), or `backend="torch"` on torch ops."""
+import ctypes as C
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -183,3 +188,193 @@ class InfoNCELoss(nn.Module):
                 f"Unique songs: {len(torch.unique(song_labels))}, "
                 f"This likely means each song only appears once in the batch.")
         return s / c
+
+
+def _raise_mrstft_refusal(msg):
+    raise RuntimeError("MultiResolutionSTFTLoss: " + msg + "; backend='torch' runs the same loss on PyTorch ops (any device, "
+                       "dtype, autograd to both arguments)")
+
+
+class _MRSTFTHip(torch.autograd.Function):
+    """(loss, components and norms) of `mst_mrstft_forward`; backward = `mst_mrstft_backward`, which recomputes the frames
+    and multiplies by the incoming gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, x, y, plan):
+        from . import _lib
+        T = x.shape[-1]
+        xr = x.detach().reshape(-1, T).contiguous()
+        yr = y.detach().reshape(-1, T).contiguous()
+        out = plan.run_forward(xr, yr)
+        ctx.save_for_backward(xr, yr, out)
+        ctx.plan, ctx.shape = plan, x.shape
+        rest = out[1:]   # components and norms
+        ctx.mark_non_differentiable(rest)
+        return out[0], rest
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_out):
+        from . import _lib
+        xr, yr, out = ctx.saved_tensors
+        plan = ctx.plan
+        rows, T = xr.shape
+        grad = torch.empty_like(xr)
+        scale = g_loss.detach().reshape(1).float().contiguous()
+        ws, need = plan.workspace(rows, T, xr.device)
+        with torch.cuda.device(xr.device):
+            _lib.check(_lib.lib().mst_mrstft_backward(_lib.dptr(xr), _lib.dptr(yr), rows, T, plan.n, plan.fft, plan.hop,
+                                                      plan.window_ptrs(xr.device), plan.sc_weight, plan.log_weight,
+                                                      _lib.dptr(out), _lib.dptr(scale), _lib.dptr(grad), _lib.dptr(ws), need,
+                                                      _lib.stream_ptr(xr.device)), "mst_mrstft_backward")
+        return grad.view(ctx.shape), None, None
+
+
+class _MRSTFTPlan:
+    """Host side of the HIP path: the resolution lists as C arrays and the fp32 window tables, built once on the host (as
+    mixing_utils.hann_window for stage A) and uploaded once per device."""
+
+    def __init__(self, fft_sizes, hop_sizes, sc_weight, log_weight):
+        self.n = len(fft_sizes)
+        self.fft_list = [int(v) for v in fft_sizes]
+        self.fft = (C.c_int * self.n)(*self.fft_list)
+        self.hop = (C.c_int * self.n)(*[int(v) for v in hop_sizes])
+        self.sc_weight, self.log_weight = float(sc_weight), float(log_weight)
+        self._windows = {}
+
+    def window_ptrs(self, device):
+        key = str(device)
+        if key not in self._windows:
+            tabs = [torch.hann_window(n).to(device) for n in self.fft_list]
+            self._windows[key] = (tabs, (C.c_void_p * self.n)(*[t.data_ptr() for t in tabs]))
+        return self._windows[key][1]
+
+    def workspace(self, rows, T, device):
+        from . import _lib
+        need = _lib.lib().mst_mrstft_workspace_bytes(self.n, self.fft, self.hop, rows, T)
+        return torch.empty(need, dtype=torch.uint8, device=device), need
+
+    def run_forward(self, xr, yr):
+        from . import _lib
+        rows, T = xr.shape
+        out = torch.empty(1 + 4 * self.n, dtype=torch.float32, device=xr.device)
+        ws, need = self.workspace(rows, T, xr.device)
+        with torch.cuda.device(xr.device):
+            _lib.check(_lib.lib().mst_mrstft_forward(_lib.dptr(xr), _lib.dptr(yr), rows, T, self.n, self.fft, self.hop,
+                                                     self.window_ptrs(xr.device), self.sc_weight, self.log_weight,
+                                                     _lib.dptr(out), _lib.dptr(ws), need, _lib.stream_ptr(xr.device)),
+                       "mst_mrstft_forward")
+        return out
+
+
+class MultiResolutionSTFTLoss(nn.Module):
+    """Drop-in for the reference MultiResolutionSTFTLoss(fft_sizes, hop_sizes, win_sizes, window)(x, y) -> scalar, x and y
+    (B, C, T) or (C, T): per resolution ||ym - xm||_F / (||ym||_F + 1e-8) + mean |log(xm + 1e-5) - log(ym + 1e-5)| of the
+    STFT magnitudes (torch.stft defaults: center, reflect padding, one-sided; periodic Hann), averaged over resolutions.
+
+    Keyword-only extensions (defaults = the reference): `sc_weight` / `log_weight` multiply the two terms;
+    `backend="hip"` runs forward and the gradient to `x` in libmst.so (CUDA fp32, `y` without gradient, win == fft in
+    {512, 1024, 2048}, hop in {n/8, n/4, n/2}, T > max(fft) // 2; anything else raises), `backend="torch"` is the plain
+    restatement on torch ops.  Neither path synchronises with the host.
+
+    `components(x, y)`: (n_resolutions, 2) unweighted (spectral convergence, log magnitude) terms, no graph."""
+
+    def __init__(self, fft_sizes=[1024, 2048, 512], hop_sizes=[256, 512, 128], win_sizes=[1024, 2048, 512], window='hann', *,
+                 sc_weight=1.0, log_weight=1.0, backend="hip"):
+        super().__init__()
+        if backend not in ("hip", "torch"):
+            raise ValueError("backend must be 'hip' or 'torch'")
+        if not (len(fft_sizes) == len(hop_sizes) == len(win_sizes)) or len(fft_sizes) < 1:
+            raise ValueError("fft_sizes, hop_sizes and win_sizes need the same length, at least 1")
+        self.fft_sizes = fft_sizes
+        self.hop_sizes = hop_sizes
+        self.win_sizes = win_sizes
+        self.window = window
+        self.sc_weight = sc_weight
+        self.log_weight = log_weight
+        self.backend = backend
+        self._plan = None
+
+    # ---- backend="torch": the reference's arithmetic, op for op
+    def stft(self, x, fft_size, hop_size, win_size):
+        if x.ndim == 2:
+            x = x.unsqueeze(0)
+        B, Cn, T = x.shape
+        window_tensor = torch.hann_window(win_size, device=x.device)   # no dtype, as the reference: fp32 table also under float64
+        return torch.stft(x.reshape(B * Cn, T), n_fft=fft_size, hop_length=hop_size, win_length=win_size, window=window_tensor,
+                          return_complex=True)
+
+    def spectral_convergence(self, x_mag, y_mag):
+        return torch.norm(y_mag - x_mag, p='fro') / (torch.norm(y_mag, p='fro') + 1e-8)
+
+    def log_stft_magnitude(self, x_mag, y_mag):
+        return F.l1_loss(torch.log(x_mag + 1e-5), torch.log(y_mag + 1e-5))
+
+    def _terms_torch(self, x, y):
+        if self.window != 'hann':
+            raise ValueError(f"window={self.window!r}: only 'hann' exists (the reference ignores the argument)")
+        terms = []
+        for fft_size, hop_size, win_size in zip(self.fft_sizes, self.hop_sizes, self.win_sizes):
+            x_mag = torch.abs(self.stft(x, fft_size, hop_size, win_size))
+            y_mag = torch.abs(self.stft(y, fft_size, hop_size, win_size))
+            terms.append((self.spectral_convergence(x_mag, y_mag), self.log_stft_magnitude(x_mag, y_mag)))
+        return terms
+
+    # ---- backend="hip"
+    def _hip_refusal(self, x, y):
+        for name, t in (("x", x), ("y", y)):
+            if not t.is_cuda:
+                return f"the HIP backend needs CUDA tensors (there is no CPU fallback), got {name} on {t.device}"
+            if t.dtype != torch.float32:
+                return f"the HIP backend is fp32, got {name} of {t.dtype}"
+        if x.shape != y.shape or x.dim() not in (2, 3):
+            return f"the HIP backend needs x and y of one shape (B, C, T) or (C, T), got {tuple(x.shape)} and {tuple(y.shape)}"
+        if x.device != y.device:
+            return f"x on {x.device} and y on {y.device}"
+        if torch.is_grad_enabled() and y.requires_grad:
+            return "the HIP backend has no gradient to the target y (detach it)"
+        if self.window != 'hann':
+            return f"the HIP backend has the Hann window only, got window={self.window!r}"
+        for n, h, w in zip(self.fft_sizes, self.hop_sizes, self.win_sizes):
+            if w != n:
+                return f"the HIP backend needs win_size == fft_size, got {w} and {n}"
+            if n not in (512, 1024, 2048):
+                return f"the HIP backend has fft_size 512, 1024 and 2048, got {n}"
+            if h not in (n // 8, n // 4, n // 2):
+                return f"the HIP backend needs hop_size in (n/8, n/4, n/2), got {h} for fft_size {n}"
+        if len(self.fft_sizes) > 16:
+            return f"the HIP backend takes up to 16 resolutions, got {len(self.fft_sizes)}"
+        if x.shape[-1] <= max(self.fft_sizes) // 2:
+            return f"the HIP backend needs T > max(fft_sizes) // 2 = {max(self.fft_sizes) // 2} samples, got T = {x.shape[-1]}"
+        if x.numel() == 0:
+            return "empty input"
+        return None
+
+    def _hip_plan(self):
+        key = (tuple(self.fft_sizes), tuple(self.hop_sizes), float(self.sc_weight), float(self.log_weight))
+        if self._plan is None or self._plan[0] != key:
+            self._plan = (key, _MRSTFTPlan(self.fft_sizes, self.hop_sizes, self.sc_weight, self.log_weight))
+        return self._plan[1]
+
+    def _hip_out(self, x, y):
+        msg = self._hip_refusal(x, y)
+        if msg:
+            _raise_mrstft_refusal(msg)
+        return _MRSTFTHip.apply(x, y, self._hip_plan())
+
+    def components(self, x, y):
+        with torch.no_grad():
+            if self.backend == "torch":
+                return torch.stack([torch.stack(t) for t in self._terms_torch(x, y)])
+            n = len(self.fft_sizes)
+            return self._hip_out(x, y)[1][:2 * n].view(n, 2).clone()
+
+    def forward(self, x, y):
+        if self.backend == "hip":
+            return self._hip_out(x, y)[0]
+        total_loss = 0.0
+        for sc_loss, log_mag_loss in self._terms_torch(x, y):
+            if self.sc_weight == 1.0 and self.log_weight == 1.0:
+                total_loss += sc_loss + log_mag_loss
+            else:
+                total_loss += self.sc_weight * sc_loss + self.log_weight * log_mag_loss
+        return total_loss / len(self.fft_sizes)
