@@ -38,84 +38,134 @@ struct FilmParams {
   float2* aff1;                                 // [B][nsub][32]
   float2* aff2;                                 // [B][nsub][64]
   int Fd, H, nsub;
+  float* h2;                                    // [B][H] second hidden layer (workspace)
+  int B;
 };
 
-#ifndef MST_FILM_U
-#define MST_FILM_U 4   // iterations of the three dot-product loops in flight (16 loads per thread): the kernel is load-latency-bound
-                     // (71 -> 45 us per 72 clips; 8 and 16 spill: 123 us)
-#endif
-__global__ __launch_bounds__(256) void film_kernel(const FilmParams p) {
-  // grid = (clip, group of sub-bands); the two small hidden layers are recomputed per group (82 k MACs)
-  extern __shared__ float sm[];
-  float* f = sm;            // [Fd]
-  float* h1 = f + p.Fd;     // [H]
-  float* h2 = h1 + p.H;     // [H]
-  float* fl = h2 + p.H;     // [bands_per_group * 192] film outputs of this group
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int bpg = (p.nsub + gridDim.y - 1) / gridDim.y;
-  const int band0 = blockIdx.y * bpg, band1 = min(p.nsub, band0 + bpg);
-  if (band0 >= band1) return;
-  for (int i = tid; i < p.Fd; i += 256) f[i] = p.feats[(size_t)b * p.Fd + i];
+// Two launches.  film_hidden_kernel computes the two hidden layers once per clip; film_head_kernel the nsub*192 outputs and
+// the folded affines.  Both work on a tile of kFilmCT clips against a slice of 64 output columns, so every weight that leaves
+// L2 feeds kFilmCT clips: thread = (column, quarter of K) with one accumulator chain per clip (a clip's numbers do not depend
+// on its neighbours in the tile), the quarters added through LDS in fixed order (q0 + q1) + (q2 + q3).
+constexpr int kFilmCT = 8;
+
+// acc[c] = sum over this thread's quarter of K of wt[i][j] * hin[i][c]; hin in LDS as [K][kFilmCT]
+__device__ __forceinline__ void film_dot(const float* __restrict__ wt, int K, int N, int j, const float* hin, int kq, float (&acc)[kFilmCT]) {
+#pragma unroll
+  for (int c = 0; c < kFilmCT; ++c) acc[c] = 0.f;
+  if (j >= N) return;
+  const int kper = (K + 3) / 4, k0 = kq * kper, k1 = min(K, k0 + kper);
+  const float* wp = wt + j;
+#pragma unroll 16
+  for (int i = k0; i < k1; ++i) {
+    const float w = wp[(size_t)i * N];
+    const float4 ha = *reinterpret_cast<const float4*>(hin + i * kFilmCT), hb = *reinterpret_cast<const float4*>(hin + i * kFilmCT + 4);
+    acc[0] = fmaf(w, ha.x, acc[0]), acc[1] = fmaf(w, ha.y, acc[1]), acc[2] = fmaf(w, ha.z, acc[2]), acc[3] = fmaf(w, ha.w, acc[3]);
+    acc[4] = fmaf(w, hb.x, acc[4]), acc[5] = fmaf(w, hb.y, acc[5]), acc[6] = fmaf(w, hb.z, acc[6]), acc[7] = fmaf(w, hb.w, acc[7]);
+  }
+}
+// red: [4 quarters][kFilmCT][64 columns].  After the barrier thread (jl, g) owns the sums of clips g and g + 4 of column jl.
+__device__ __forceinline__ void film_reduce(float* red, const float (&acc)[kFilmCT], int jl, int kq, float (&out)[2]) {
+#pragma unroll
+  for (int c = 0; c < kFilmCT; ++c) red[(kq * kFilmCT + c) * 64 + jl] = acc[c];
   __syncthreads();
-  for (int j = tid; j < p.H; j += 256) {
-    float a0 = p.b0[j], a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    int i = 0;
-#pragma unroll MST_FILM_U
-    for (; i + 3 < p.Fd; i += 4) {
-      a0 = fmaf(p.w0t[(size_t)i * p.H + j], f[i], a0);
-      a1 = fmaf(p.w0t[(size_t)(i + 1) * p.H + j], f[i + 1], a1);
-      a2 = fmaf(p.w0t[(size_t)(i + 2) * p.H + j], f[i + 2], a2);
-      a3 = fmaf(p.w0t[(size_t)(i + 3) * p.H + j], f[i + 3], a3);
-    }
-    for (; i < p.Fd; ++i) a0 = fmaf(p.w0t[(size_t)i * p.H + j], f[i], a0);
-    h1[j] = fmaxf((a0 + a1) + (a2 + a3), 0.f);
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int c = kq + 4 * r;
+    out[r] = (red[(0 * kFilmCT + c) * 64 + jl] + red[(1 * kFilmCT + c) * 64 + jl]) +
+             (red[(2 * kFilmCT + c) * 64 + jl] + red[(3 * kFilmCT + c) * 64 + jl]);
+  }
+}
+
+__global__ __launch_bounds__(256) void film_hidden_kernel(const FilmParams p) {
+  // grid = (clip tile, 64-column slice of the second hidden layer); the first layer (Fd x H MACs per clip) is recomputed per slice
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* f = sm;                           // [Fd][kFilmCT]
+  float* h1 = f + p.Fd * kFilmCT;          // [H][kFilmCT]
+  float* red = h1 + p.H * kFilmCT;         // [4][kFilmCT][64]
+  const int tid = threadIdx.x, jl = tid & 63, kq = tid >> 6;
+  const int b0 = blockIdx.x * kFilmCT;
+  for (int idx = tid; idx < p.Fd * kFilmCT; idx += 256) {
+    const int c = idx / p.Fd, i = idx % p.Fd;
+    f[i * kFilmCT + c] = b0 + c < p.B ? p.feats[(size_t)(b0 + c) * p.Fd + i] : 0.f;
   }
   __syncthreads();
-  for (int j = tid; j < p.H; j += 256) {
-    float a0 = p.b3[j], a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    int i = 0;
-#pragma unroll MST_FILM_U
-    for (; i + 3 < p.H; i += 4) {
-      a0 = fmaf(p.w3t[(size_t)i * p.H + j], h1[i], a0);
-      a1 = fmaf(p.w3t[(size_t)(i + 1) * p.H + j], h1[i + 1], a1);
-      a2 = fmaf(p.w3t[(size_t)(i + 2) * p.H + j], h1[i + 2], a2);
-      a3 = fmaf(p.w3t[(size_t)(i + 3) * p.H + j], h1[i + 3], a3);
+  float acc[kFilmCT], out[2];
+  for (int j0 = 0; j0 < p.H; j0 += 64) {
+    film_dot(p.w0t, p.Fd, p.H, j0 + jl, f, kq, acc);
+    film_reduce(red, acc, jl, kq, out);
+    if (j0 + jl < p.H) {
+      const float bias = p.b0[j0 + jl];
+      h1[(j0 + jl) * kFilmCT + kq] = fmaxf(out[0] + bias, 0.f);
+      h1[(j0 + jl) * kFilmCT + kq + 4] = fmaxf(out[1] + bias, 0.f);
     }
-    for (; i < p.H; ++i) a0 = fmaf(p.w3t[(size_t)i * p.H + j], h1[i], a0);
-    h2[j] = fmaxf((a0 + a1) + (a2 + a3), 0.f);
+    __syncthreads();   // h1 complete after the last pass; red free for the next
+  }
+  const int j = blockIdx.y * 64 + jl;
+  film_dot(p.w3t, p.H, p.H, j, h1, kq, acc);
+  film_reduce(red, acc, jl, kq, out);
+  if (j < p.H) {
+    const float bias = p.b3[j];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+      if (b0 + kq + 4 * r < p.B) p.h2[(size_t)(b0 + kq + 4 * r) * p.H + j] = fmaxf(out[r] + bias, 0.f);
+  }
+}
+
+__global__ __launch_bounds__(256) void film_head_kernel(const FilmParams p) {
+  // grid = (clip tile, band * 3 + slice).  A band's 192 outputs are [gamma1 32][beta1 32][gamma2 64][beta2 64]; a slice holds 32
+  // gammas and their 32 betas, so that the folded affine pair comes out of one workgroup:
+  //   slice 0: columns 0..63;  slice 1: 64..95 and 128..159;  slice 2: 96..127 and 160..191
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* h2 = sm;                          // [H][kFilmCT]
+  float* red = h2 + p.H * kFilmCT;         // [4][kFilmCT][64]
+  float* fl = red + 4 * kFilmCT * 64;      // [kFilmCT][64] outputs of this slice
+  const int tid = threadIdx.x, jl = tid & 63, kq = tid >> 6;
+  const int b0 = blockIdx.x * kFilmCT;
+  const int band = blockIdx.y / 3, slice = blockIdx.y % 3;
+  for (int idx = tid; idx < p.H * kFilmCT; idx += 256) {
+    const int c = idx / p.H, i = idx % p.H;
+    h2[i * kFilmCT + c] = b0 + c < p.B ? p.h2[(size_t)(b0 + c) * p.H + i] : 0.f;
   }
   __syncthreads();
   const int nout = p.nsub * 192;
-  float* film = p.film + (size_t)b * nout;
-  for (int o = band0 * 192 + tid; o < band1 * 192; o += 256) {
-    float a0 = p.hb[o], a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    int i = 0;
-#pragma unroll MST_FILM_U
-    for (; i + 3 < p.H; i += 4) {
-      a0 = fmaf(p.hwt[(size_t)i * nout + o], h2[i], a0);
-      a1 = fmaf(p.hwt[(size_t)(i + 1) * nout + o], h2[i + 1], a1);
-      a2 = fmaf(p.hwt[(size_t)(i + 2) * nout + o], h2[i + 2], a2);
-      a3 = fmaf(p.hwt[(size_t)(i + 3) * nout + o], h2[i + 3], a3);
-    }
-    for (; i < p.H; ++i) a0 = fmaf(p.hwt[(size_t)i * nout + o], h2[i], a0);
-    const float v = (a0 + a1) + (a2 + a3);
-    film[o] = v;
-    fl[o - band0 * 192] = v;
+  const int col = slice == 0 ? jl : (jl < 32 ? 32 + 32 * slice + jl : 96 + 32 * slice + (jl - 32));
+  const int o = band * 192 + col;
+  float acc[kFilmCT], out[2];
+  film_dot(p.hwt, p.H, nout, o, h2, kq, acc);
+  film_reduce(red, acc, jl, kq, out);
+  const float bias = p.hb[o];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int c = kq + 4 * r;
+    const float v = out[r] + bias;
+    fl[c * 64 + jl] = v;
+    if (b0 + c < p.B) p.film[(size_t)(b0 + c) * nout + o] = v;
   }
   __syncthreads();
-  for (int idx = band0 * 96 + tid; idx < band1 * 96; idx += 256) {
-    const int band = idx / 96, c = idx % 96;
-    const float* fb = fl + (band - band0) * 192;
-    if (c < 32) {
-      const float g = fb[c], be = fb[32 + c];
-      p.aff1[((size_t)b * p.nsub + band) * 32 + c] = make_float2(g * p.s1[band * 32 + c], fmaf(g, p.t1[band * 32 + c], be));
+  for (int idx = tid; idx < kFilmCT * 32; idx += 256) {
+    const int c = idx >> 5, ch = idx & 31, b = b0 + c;
+    if (b >= p.B) continue;
+    const float g = fl[c * 64 + ch], be = fl[c * 64 + 32 + ch];
+    if (slice == 0) {
+      p.aff1[((size_t)b * p.nsub + band) * 32 + ch] = make_float2(g * p.s1[band * 32 + ch], fmaf(g, p.t1[band * 32 + ch], be));
     } else {
-      const int c2 = c - 32;
-      const float g = fb[64 + c2], be = fb[128 + c2];
-      p.aff2[((size_t)b * p.nsub + band) * 64 + c2] =
-          make_float2(g * p.s2[band * 64 + c2], fmaf(g, p.t2[band * 64 + c2], be));
+      const int c2 = 32 * (slice - 1) + ch;
+      p.aff2[((size_t)b * p.nsub + band) * 64 + c2] = make_float2(g * p.s2[band * 64 + c2], fmaf(g, p.t2[band * 64 + c2], be));
     }
   }
+}
+
+// dynamic LDS of the larger of the two kernels; mst_encoder_create refuses dimensions beyond the 64 KB every kernel may ask for
+constexpr size_t film_lds_bytes(int Fd, int H) {
+  return (size_t)((Fd + H) * kFilmCT + 5 * kFilmCT * 64) * sizeof(float);
+}
+hipError_t launch_film(const FilmParams& fp, hipStream_t st) {
+  const int tiles = (fp.B + kFilmCT - 1) / kFilmCT;
+  const size_t lds_h = (size_t)((fp.Fd + fp.H) * kFilmCT + 4 * kFilmCT * 64) * sizeof(float);
+  const size_t lds_o = (size_t)(fp.H * kFilmCT + 5 * kFilmCT * 64) * sizeof(float);
+  hipLaunchKernelGGL(film_hidden_kernel, dim3(tiles, (fp.H + 63) / 64), dim3(256), lds_h, st, fp);
+  hipLaunchKernelGGL(film_head_kernel, dim3(tiles, fp.nsub * 3), dim3(256), lds_o, st, fp);
+  return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2173,60 +2223,63 @@ __global__ __launch_bounds__(kConvThreads) void conv2_f16x3_kernel(const ConvPar
 
 // ------------------------------------------------------------------------------------------
 // Attention scores: s[b][t] = w2 . tanh(W1 x[b,:,t] + b1) + b2      (model.py:198-200)
-// fp32-MFMA GEMM.  One workgroup = 16 frames; its 4 waves split the 256 hidden units (4 N-tiles each) and
-// combine their partial dot products through LDS.  W1 is pre-swizzled into B-fragment order.
+// fp32-MFMA GEMM.  One workgroup = kAttnMT M-tiles (64 frames) x kAttnNT N-tiles (128 of the 256 hidden units): every weight
+// fragment that leaves L2 feeds kAttnMT MFMAs.  Its 4 waves split K in four fixed quarters (the quarter of a k-step does not
+// depend on B) and add their accumulators through LDS in wave order; wave w then finishes M-tile w.  The two halves of the
+// hidden units leave two partial scores per frame, part[half][b][t]; whoever reads the scores adds them: (p0 + p1) + b2.
+// W1 is pre-swizzled into B-fragment order.
 // ------------------------------------------------------------------------------------------
 struct AttnParams {
   const float* x;       // pool_in [B][C][W]
   const float* w1frag;  // [C/4][16][64]
   const float *b1, *w2;
-  const float* b2;      // device [1]
-  float* scores;        // [B][W]
+  float* part;          // [2][B][W] partial scores (without b2)
   int B, C, W, A;
 };
 
-#ifndef MST_ATTN_MT
-#define MST_ATTN_MT 1
-#endif
 #ifndef MST_ATTN_U
-#define MST_ATTN_U 2
+#define MST_ATTN_U 4
 #endif
-constexpr int kAttnMT = MST_ATTN_MT;   // M-tiles (16 frames each) per workgroup: every weight fragment fetched from L2 feeds kAttnMT MFMAs
+constexpr int kAttnMT = 4;             // M-tiles (16 frames each) per workgroup; the epilogue gives one to each of the 4 waves
+constexpr int kAttnNT = 8;             // N-tiles per workgroup: half of the hidden units
+constexpr int kAttnHalves = 2;
+constexpr size_t kAttnLds = (size_t)kAttnMT * 3 * kAttnNT * 256 * sizeof(float);
 __global__ __launch_bounds__(256) void attn_scores_kernel(const AttnParams p) {
-  __shared__ float part_s[4][16 * kAttnMT];
+  extern __shared__ float red[];   // [M-tile][the 3 waves that do not own it][N-tile][4 regs][64 lanes]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int mt = blockIdx.x;
+  const int mb = blockIdx.x, nh = blockIdx.y;
   const int M = p.B * p.W;
   const int kq = lane >> 4, i = lane & 15;
   const float* xa[kAttnMT];
   bool ok[kAttnMT];
 #pragma unroll
   for (int q = 0; q < kAttnMT; ++q) {
-    const int m = (mt * kAttnMT + q) * 16 + i;
+    const int m = (mb * kAttnMT + q) * 16 + i;
     ok[q] = m < M;
     const int b = ok[q] ? m / p.W : 0, t = ok[q] ? m % p.W : 0;
     xa[q] = p.x + ((size_t)b * p.C + kq) * p.W + t;
   }
-  f32x4 acc[kAttnMT][4];
+  f32x4 acc[kAttnMT][kAttnNT];
 #pragma unroll
   for (int q = 0; q < kAttnMT; ++q)
 #pragma unroll
-    for (int n = 0; n < 4; ++n) acc[q][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < kAttnNT; ++n) acc[q][n] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int steps = p.C / 4;
-  const float* wf = p.w1frag + (size_t)(wave * 4) * 64 + lane;
+  const int s0 = wave * steps / 4, s1 = (wave + 1) * steps / 4;   // this wave's quarter of K
+  const float* wf = p.w1frag + (size_t)(nh * kAttnNT) * 64 + lane;
   // software-pipelined over batches of kAttnU k-steps: the loads of batch j + 1 are in flight while the MFMAs of batch j run
-  // (the loop is load-latency-bound: one wave per SIMD and a half, 352 dependent-free k-steps)
+  // (kAttnU * 12 loads of 256 B per wave against kAttnU * 32 MFMAs)
   constexpr int kAttnU = MST_ATTN_U;
-  float a[2][kAttnU][kAttnMT], bb[2][kAttnU][4];
+  float a[2][kAttnU][kAttnMT], bb[2][kAttnU][kAttnNT];
   auto load_batch = [&](int sb, int buf) __attribute__((always_inline)) {
 #pragma unroll
     for (int u = 0; u < kAttnU; ++u) {
-      const int s = min(sb + u, steps - 1);
+      const int s = min(sb + u, s1 - 1);
 #pragma unroll
       for (int q = 0; q < kAttnMT; ++q)
-        a[buf][u][q] = (ok[q] && sb + u < steps) ? xa[q][(size_t)s * 4 * p.W] : 0.f;   // a zero A fragment makes a padded step a no-op
+        a[buf][u][q] = (ok[q] && sb + u < s1) ? xa[q][(size_t)s * 4 * p.W] : 0.f;   // a zero A fragment makes a padded step a no-op
 #pragma unroll
-      for (int n = 0; n < 4; ++n) bb[buf][u][n] = wf[((size_t)s * 16 + n) * 64];
+      for (int n = 0; n < kAttnNT; ++n) bb[buf][u][n] = wf[((size_t)s * 16 + n) * 64];
     }
   };
   auto mfma_batch = [&](int buf) __attribute__((always_inline)) {
@@ -2235,60 +2288,88 @@ __global__ __launch_bounds__(256) void attn_scores_kernel(const AttnParams p) {
 #pragma unroll
       for (int q = 0; q < kAttnMT; ++q)
 #pragma unroll
-        for (int n = 0; n < 4; ++n) acc[q][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[buf][u][q], bb[buf][u][n], acc[q][n], 0, 0, 0);
+        for (int n = 0; n < kAttnNT; ++n) acc[q][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[buf][u][q], bb[buf][u][n], acc[q][n], 0, 0, 0);
   };
-  load_batch(0, 0);
-  for (int sb = 0; sb < steps; sb += 2 * kAttnU) {   // (a batch past the end loads clamped addresses and multiplies zeros)
-    load_batch(sb + kAttnU, 1);
-    mfma_batch(0);
-    load_batch(sb + 2 * kAttnU, 0);
-    mfma_batch(1);
+  if (s0 < s1) {
+    load_batch(s0, 0);
+    for (int sb = s0; sb < s1; sb += 2 * kAttnU) {   // (a batch past the end loads clamped addresses and multiplies zeros)
+      load_batch(sb + kAttnU, 1);
+      mfma_batch(0);
+      load_batch(sb + 2 * kAttnU, 0);
+      mfma_batch(1);
+    }
   }
-  // rows 4*kq + r of an M-tile live in lane group kq; columns (wave*4 + n)*16 + i
+  // K reduction over the waves: wave w keeps M-tile w and hands the other three to their owners
+  f32x4 own[kAttnNT];
 #pragma unroll
-  for (int q = 0; q < kAttnMT; ++q)
+  for (int q = 0; q < kAttnMT; ++q) {
+    if (q == wave) {
+#pragma unroll
+      for (int n = 0; n < kAttnNT; ++n) own[n] = acc[q][n];
+    } else {
+      float* dst = red + ((size_t)(q * 3 + (wave < q ? wave : wave - 1)) * kAttnNT) * 256 + lane;
+#pragma unroll
+      for (int n = 0; n < kAttnNT; ++n)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dst[n * 256 + r * 64] = acc[q][n][r];
+    }
+  }
+  __syncthreads();
+  // rows 4*kq + r of M-tile `wave` live in lane group kq; columns (nh*kAttnNT + n)*16 + i.  The four K quarters are added in
+  // wave order, (q0 + q1) + (q2 + q3), whichever wave owns the tile.
+  float part[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int n = 0; n < kAttnNT; ++n) {
+    const int h = (nh * kAttnNT + n) * 16 + i;
+    const float w2 = p.w2[h], b1 = p.b1[h];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      float part = 0.f;
+      float q4[4];
 #pragma unroll
-      for (int n = 0; n < 4; ++n) {
-        const int h = (wave * 4 + n) * 16 + i;
-        part = fmaf(p.w2[h], tanhf(acc[q][n][r] + p.b1[h]), part);
-      }
-#pragma unroll
-      for (int o = 8; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
-      if (i == 0) part_s[wave][16 * q + 4 * kq + r] = part;
+      for (int w = 0; w < 4; ++w)
+        q4[w] = w == wave ? own[n][r] : red[((size_t)(wave * 3 + (w < wave ? w : w - 1)) * kAttnNT + n) * 256 + r * 64 + lane];
+      part[r] = fmaf(w2, tanhf((q4[0] + q4[1]) + (q4[2] + q4[3]) + b1), part[r]);
     }
-  __syncthreads();
-  if (threadIdx.x < 16 * kAttnMT) {
-    const int mr = mt * 16 * kAttnMT + threadIdx.x;
-    if (mr < M)
-      p.scores[mr] = ((part_s[0][threadIdx.x] + part_s[1][threadIdx.x]) + (part_s[2][threadIdx.x] + part_s[3][threadIdx.x])) + p.b2[0];
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float v = part[r];
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int m = (mb * kAttnMT + wave) * 16 + 4 * kq + r;
+    if (i == 0 && m < M) p.part[(size_t)nh * M + m] = v;
   }
 }
 
 // softmax over frames + weighted sum: pooled[b][c] = sum_t softmax(s[b])[t] * x[b][c][t]   (model.py:201-206)
 struct PoolParams {
   const float* x;       // [B][C][W]
-  const float* scores;  // [B][W]
+  const float* part;    // [2][B][W] partial scores of attn_scores_kernel
+  const float* b2;      // device [1]
   float* pooled;        // [B][C]
   int C, W;
+  long long M;          // B * W: stride between the two partial-score planes
 };
 
 __global__ __launch_bounds__(256) void attn_pool_kernel(const PoolParams p) {
   extern __shared__ float sm[];
-  float* w = sm;  // [W] normalised weights
+  float* w = sm;  // [W] scores, then unnormalised weights
   __shared__ float red[8];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float b2 = p.b2[0];
   float mx = -INFINITY;
-  for (int t = tid; t < p.W; t += 256) mx = fmaxf(mx, p.scores[(size_t)b * p.W + t]);
+  for (int t = tid; t < p.W; t += 256) {
+    const float s = (p.part[(size_t)b * p.W + t] + p.part[(size_t)p.M + (size_t)b * p.W + t]) + b2;
+    w[t] = s;
+    mx = fmaxf(mx, s);
+  }
   mx = mst::wave_max(mx);
   if (lane == 0) red[wave] = mx;
   __syncthreads();
   mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   float sum = 0.f;
-  for (int t = tid; t < p.W; t += 256) {
-    const float e = expf(p.scores[(size_t)b * p.W + t] - mx);
+  for (int t = tid; t < p.W; t += 256) {   // (every thread re-reads only what it wrote)
+    const float e = expf(w[t] - mx);
     w[t] = e;
     sum += e;
   }
@@ -2312,7 +2393,8 @@ __global__ __launch_bounds__(256) void attn_pool_kernel(const PoolParams p) {
 }
 
 // projection + ReLU: emb[b][e] = relu(bp[e] + sum_c Wp[e][c] pooled[b][c])   (model.py:208-209)
-// fp32-MFMA GEMM, one wave = one 16-column tile of E x up to 8 row tiles of clips; Wp in B-fragment order.
+// fp32-MFMA GEMM, one workgroup = one 16-column tile of E x one row tile of 16 clips (grid E/16 x ceil(B/16): 240 workgroups
+// at 72 clips); Wp in B-fragment order.  The partition of K does not depend on B.
 struct ProjParams {
   const float* pooled;  // [B][C]
   const float* wfrag;   // [C/4][E/16][64]
@@ -2321,61 +2403,55 @@ struct ProjParams {
   int B, C, E;
 };
 
-template <int MT>
+constexpr int kProjU = 8;   // k-steps of loads in flight per wave
 __global__ __launch_bounds__(512) void proj_kernel(const ProjParams p) {
-  // one workgroup = one 16-column tile of E x MT row tiles of clips; its 8 waves split K (split-K inside the
-  // workgroup, LDS reduce); every wave keeps 4 k-steps of loads in flight (the plain loop was latency-bound)
-  extern __shared__ float red[];  // [8 waves][MT * 4 regs][64 lanes]
+  // its 8 waves split K in eighths (split-K inside the workgroup, LDS reduce in wave order)
+  __shared__ float red[8][4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nt = blockIdx.x, NTE = p.E / 16;
   const int kq = lane >> 4, i = lane & 15;
-  const int m0 = blockIdx.y * (16 * MT);
-  f32x4 acc[MT];
-  const float* ap[MT];
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-    acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    ap[t] = p.pooled + (size_t)min(m0 + t * 16 + i, p.B - 1) * p.C + kq;   // rows past B are computed and dropped
-  }
+  const int m0 = blockIdx.y * 16;
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+  const float* ap = p.pooled + (size_t)min(m0 + i, p.B - 1) * p.C + kq;   // rows past B are computed and dropped
   const float* wf = p.wfrag + (size_t)nt * 64 + lane;
   const int steps = p.C / 4;
   const int s0 = wave * steps / 8, s1 = (wave + 1) * steps / 8;
-  for (int sb = s0; sb < s1; sb += 4) {
-    float bb[4], a[4][MT];
+  for (int sb = s0; sb < s1; sb += kProjU) {
+    float bb[kProjU], a[kProjU];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
+    for (int u = 0; u < kProjU; ++u) {
       const int s = min(sb + u, s1 - 1);
       bb[u] = (sb + u < s1) ? wf[(size_t)s * NTE * 64] : 0.f;   // a zero B fragment makes the padded step a no-op
-#pragma unroll
-      for (int t = 0; t < MT; ++t) a[u][t] = ap[t][4 * s];
+      a[u] = ap[4 * s];
     }
 #pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int t = 0; t < MT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][t], bb[u], acc[t], 0, 0, 0);
+    for (int u = 0; u < kProjU; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], bb[u], acc, 0, 0, 0);
   }
 #pragma unroll
-  for (int t = 0; t < MT; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) red[(wave * (4 * MT) + t * 4 + r) * 64 + lane] = acc[t][r];
+  for (int r = 0; r < 4; ++r) red[wave][r][lane] = acc[r];
   __syncthreads();
-  const int e = nt * 16 + i;
-  const float be = p.bias[e];
-  for (int t = wave; t < MT; t += 8) {  // wave w finalises tiles w, w+8, ...
+  if (wave < 4) {   // wave r finalises accumulator register r: rows 4*kq + r
+    const int e = nt * 16 + i, m = m0 + 4 * kq + wave;
+    float v = 0.f;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float v = 0.f;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) v += red[(w * (4 * MT) + t * 4 + r) * 64 + lane];
-      const int m = m0 + t * 16 + 4 * kq + r;
-      if (m < p.B) p.emb[(size_t)m * p.E + e] = fmaxf(v + be, 0.f);
-    }
+    for (int w = 0; w < 8; ++w) v += red[w][wave][lane];
+    if (m < p.B) p.emb[(size_t)m * p.E + e] = fmaxf(v + p.bias[e], 0.f);
   }
 }
 
-template <int MT>
-void launch_proj(const ProjParams& pj, int ygrid, hipStream_t st) {
-  hipLaunchKernelGGL((proj_kernel<MT>), dim3(pj.E / 16, ygrid), dim3(512), (size_t)8 * 4 * MT * 64 * sizeof(float), st, pj);
+hipError_t launch_attn_scores(const AttnParams& ap, hipStream_t st) {
+  static unsigned long long attr = 0;   // per-device bit mask: the attribute belongs to the device
+  if (mst::first_use_on_device(attr)) {
+    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_scores_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnLds);
+    if (err != hipSuccess) return err;
+  }
+  const int mblocks = (ap.B * ap.W + 16 * kAttnMT - 1) / (16 * kAttnMT);
+  hipLaunchKernelGGL(attn_scores_kernel, dim3(mblocks, kAttnHalves), dim3(256), kAttnLds, st, ap);
+  return hipGetLastError();
+}
+
+void launch_proj(const ProjParams& pj, hipStream_t st) {
+  hipLaunchKernelGGL(proj_kernel, dim3(pj.E / 16, (pj.B + 15) / 16), dim3(512), 0, st, pj);
 }
 
 }  // namespace
@@ -2476,7 +2552,7 @@ inline bool train_fwd16(const mst_encoder* e) { return e->train_f16 != 0; }
 inline bool train_bwd16(const mst_encoder* e) { return e->train_f16 != 0; }
 
 struct WsLayout {
-  size_t film, aff1, aff2, pool1, pool1_h16, pool1_l16, f16scale, xmax, pool_in, scores, pooled, total;
+  size_t film, film_h2, aff1, aff2, pool1, pool1_h16, pool1_l16, f16scale, xmax, pool_in, scores, pooled, total;
   int W1, W2;
 };
 
@@ -2492,6 +2568,7 @@ WsLayout ws_layout(const mst_encoder* e, int B, int frames) {
     return at;
   };
   L.film = take((size_t)B * ns * 192 * 4);
+  L.film_h2 = take((size_t)B * e->cfg.film_hidden * 4);
   L.aff1 = take((size_t)B * ns * 32 * 8);
   L.aff2 = take((size_t)B * ns * 64 * 8);
   L.pool1 = take((size_t)B * ns * 32 * e->H1 * L.W1 * 4);
@@ -2500,7 +2577,7 @@ WsLayout ws_layout(const mst_encoder* e, int B, int frames) {
   L.f16scale = take(e->conv1_f16x3 >= 2 ? (size_t)B * ns * 2 * 4 : 0);
   L.xmax = take(e->conv1_f16x3 >= 2 ? (size_t)B * 4 : 0);
   L.pool_in = take((size_t)B * e->C * L.W2 * 4);
-  L.scores = take((size_t)B * L.W2 * 4);
+  L.scores = take((size_t)kAttnHalves * B * L.W2 * 4);   // attn_scores_kernel's two partial-score planes
   L.pooled = take((size_t)B * e->C * 4);
   L.total = o;
   return L;
@@ -3479,6 +3556,9 @@ int mst_encoder_create(mst_encoder** out, const mst_encoder_config* cfg, const m
               cfg->split_size, sub);
   MST_REQUIRE(cfg->attn_hidden == 256, "mst_encoder_create: attn_hidden must be 256 (got %d)", cfg->attn_hidden);
   MST_REQUIRE(cfg->feature_dim >= 1 && cfg->film_hidden >= 1 && cfg->embed_dim >= 1, "mst_encoder_create: bad dims");
+  MST_REQUIRE(film_lds_bytes(cfg->feature_dim, cfg->film_hidden) <= 64 * 1024,
+              "mst_encoder_create: feature_dim=%d + film_hidden=%d exceed the FiLM kernels' LDS tile (8 clips x (feature_dim + film_hidden) "
+              "floats + 10 KB <= 64 KB)", cfg->feature_dim, cfg->film_hidden);
   for (const float* const* q = &w->conv1_w; q <= &w->proj_b; ++q)
     MST_REQUIRE(*q != nullptr, "mst_encoder_create: NULL weight pointer");
   mst_encoder* e = new mst_encoder();
@@ -3721,12 +3801,8 @@ int mst_encoder_forward_in(const mst_encoder* e, const mst_logmel_in* lin, int f
   mark(0);
   {
     FilmParams fp{feats, e->w0t, e->b0, e->w3t, e->b3, e->hwt, e->hb, e->s1, e->t1, e->s2, e->t2,
-                  film, aff1, aff2, e->cfg.feature_dim, e->cfg.film_hidden, ns};
-    const int groups = ns < 4 ? ns : 4;
-    const int bpg = (ns + groups - 1) / groups;
-    const size_t lds = (size_t)(e->cfg.feature_dim + 2 * e->cfg.film_hidden + bpg * 192) * sizeof(float);
-    hipLaunchKernelGGL(film_kernel, dim3(B, groups), dim3(256), lds, st, fp);
-    MST_HIP_CHECK(hipGetLastError());
+                  film, aff1, aff2, e->cfg.feature_dim, e->cfg.film_hidden, ns, reinterpret_cast<float*>(ws + L.film_h2), B};
+    MST_HIP_CHECK(launch_film(fp, st));
   }
   mark(1);
   const int grid = e->num_cus;
@@ -3929,25 +4005,18 @@ int mst_encoder_forward_in(const mst_encoder* e, const mst_logmel_in* lin, int f
   }
   mark(3);
   {
-    AttnParams ap{pool_in, e->att0frag, e->att0_b, e->att2_w, e->att2_b, scores, B, e->C, L.W2, e->cfg.attn_hidden};
-    const int mtiles = (B * L.W2 + 16 * kAttnMT - 1) / (16 * kAttnMT);
-    hipLaunchKernelGGL(attn_scores_kernel, dim3(mtiles), dim3(256), 0, st, ap);
-    MST_HIP_CHECK(hipGetLastError());
+    AttnParams ap{pool_in, e->att0frag, e->att0_b, e->att2_w, scores, B, e->C, L.W2, e->cfg.attn_hidden};
+    MST_HIP_CHECK(launch_attn_scores(ap, st));
   }
   mark(4);
   {
     float* pooled = reinterpret_cast<float*>(ws + L.pooled);
-    PoolParams pp{pool_in, scores, pooled, e->C, L.W2};
+    PoolParams pp{pool_in, scores, e->att2_b, pooled, e->C, L.W2, (long long)B * L.W2};
     const int slices = (e->C + 127) / 128;
     hipLaunchKernelGGL(attn_pool_kernel, dim3(B, slices), dim3(256), (size_t)((L.W2 + 3) & ~3) * sizeof(float), st, pp);
     MST_HIP_CHECK(hipGetLastError());
     ProjParams pj{pooled, e->projfrag, e->proj_b, emb, B, e->C, e->cfg.embed_dim};
-    const int mt_all = (B + 15) / 16;   // row tiles of clips
-    if (mt_all <= 1) launch_proj<1>(pj, 1, st);
-    else if (mt_all <= 2) launch_proj<2>(pj, 1, st);
-    else if (mt_all <= 3) launch_proj<3>(pj, 1, st);
-    else if (mt_all <= 5) launch_proj<5>(pj, 1, st);
-    else launch_proj<8>(pj, (B + 127) / 128, st);
+    launch_proj(pj, st);
     MST_HIP_CHECK(hipGetLastError());
   }
   mark(5);
@@ -4091,12 +4160,8 @@ int mst_encoder_forward_train_in(const mst_encoder* e, const mst_logmel_in* lin,
     MST_HIP_CHECK(hipMemcpyAsync(film, taps->film_in, (size_t)B * ns * 192 * 4, hipMemcpyDeviceToDevice, st));
   } else {   // FiLM MLP (its eval-mode affines are overwritten by bn_fold_kernel below)
     FilmParams fp{feats, e->w0t, e->b0, e->w3t, e->b3, e->hwt, e->hb, e->s1, e->t1, e->s2, e->t2,
-                  film, aff1, aff2, e->cfg.feature_dim, e->cfg.film_hidden, ns};
-    const int groups = ns < 4 ? ns : 4;
-    const int bpg = (ns + groups - 1) / groups;
-    const size_t lds = (size_t)(e->cfg.feature_dim + 2 * e->cfg.film_hidden + bpg * 192) * sizeof(float);
-    hipLaunchKernelGGL(film_kernel, dim3(B, groups), dim3(256), lds, st, fp);
-    MST_HIP_CHECK(hipGetLastError());
+                  film, aff1, aff2, e->cfg.feature_dim, e->cfg.film_hidden, ns, reinterpret_cast<float*>(ws + L.film_h2), B};
+    MST_HIP_CHECK(launch_film(fp, st));
   }
   {   // conv1 raw + statistics
     ConvParams cp{};
@@ -4297,22 +4362,15 @@ int mst_encoder_forward_train_in(const mst_encoder* e, const mst_logmel_in* lin,
     MST_HIP_CHECK(hipGetLastError());
   }
   if (emb) {   // attention pooling head (emb == NULL: the caller runs its own head on pool_in)
-    AttnParams ap{pool_in, e->att0frag, e->att0_b, e->att2_w, e->att2_b, scores, B, e->C, L.W2, e->cfg.attn_hidden};
-    const int mtiles = (B * L.W2 + 16 * kAttnMT - 1) / (16 * kAttnMT);
-    hipLaunchKernelGGL(attn_scores_kernel, dim3(mtiles), dim3(256), 0, st, ap);
-    MST_HIP_CHECK(hipGetLastError());
+    AttnParams ap{pool_in, e->att0frag, e->att0_b, e->att2_w, scores, B, e->C, L.W2, e->cfg.attn_hidden};
+    MST_HIP_CHECK(launch_attn_scores(ap, st));
     float* pooled = reinterpret_cast<float*>(ws + L.pooled);
-    PoolParams pp{pool_in, scores, pooled, e->C, L.W2};
+    PoolParams pp{pool_in, scores, e->att2_b, pooled, e->C, L.W2, (long long)B * L.W2};
     const int slices = (e->C + 127) / 128;
     hipLaunchKernelGGL(attn_pool_kernel, dim3(B, slices), dim3(256), (size_t)((L.W2 + 3) & ~3) * sizeof(float), st, pp);
     MST_HIP_CHECK(hipGetLastError());
     ProjParams pj{pooled, e->projfrag, e->proj_b, emb, B, e->C, e->cfg.embed_dim};
-    const int mt_all = (B + 15) / 16;
-    if (mt_all <= 1) launch_proj<1>(pj, 1, st);
-    else if (mt_all <= 2) launch_proj<2>(pj, 1, st);
-    else if (mt_all <= 3) launch_proj<3>(pj, 1, st);
-    else if (mt_all <= 5) launch_proj<5>(pj, 1, st);
-    else launch_proj<8>(pj, (B + 127) / 128, st);
+    launch_proj(pj, st);
     MST_HIP_CHECK(hipGetLastError());
   }
   if (taps && taps->film) MST_HIP_CHECK(hipMemcpyAsync(taps->film, film, (size_t)B * ns * 192 * 4, hipMemcpyDeviceToDevice, st));

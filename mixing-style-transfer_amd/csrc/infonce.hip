@@ -25,54 +25,77 @@ __global__ __launch_bounds__(256) void l2norm_kernel(const float* emb, float* in
   if (tid == 0) inv_norm[r] = 1.0f / fmaxf(sqrtf((red[0] + red[1]) + (red[2] + red[3])), 1e-12f);  // F.normalize eps
 }
 
-__global__ __launch_bounds__(256) void infonce_rows_kernel(const float* emb, const int64_t* labels, const float* inv_norm,
-                                                           float* sim, int N, int D, int row0, float inv_tau, float* rowout) {
+// Forward: two launches (three before).  Workgroup = one local anchor row i: every wave forms the inverse norms it needs itself
+// (its own columns' and the anchor's, from the same loads as the dot products; a wave's sum of squares is 64 strided partial
+// sums met in wave_sum's tree, the same bits in whichever workgroup or wave computes it), writes S_i. and the row's
+// (loss, has-positive) pair; infonce_reduce_kernel adds the pairs in a fixed tree.  No float atomics, no state between
+// workgroups or between calls: the loss is bit-identical from run to run (the reference's deterministic mode, src/train.py:30).
+// (Folding the reduction into this launch needs an arrival counter that is zero at every start: a memset node per call, i.e. the
+// launch it would save, or state outside the caller's workspace, which the ABI rules out.  Tried with library-owned counters,
+// 23.3 us for the single launch; dropped for that reason.)
+constexpr int kInfoThreads = 512, kInfoWaves = kInfoThreads / 64;
+__global__ __launch_bounds__(kInfoThreads) void infonce_fwd_kernel(const float* __restrict__ emb, const int64_t* __restrict__ labels,
+                                                                   float* sim, int N, int D, int row0, float inv_tau, float* rowout) {
   extern __shared__ float srow[];  // [D] normalised anchor
-  __shared__ float red[12];
+  __shared__ float red[3 * kInfoWaves];
   const int i = row0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float ni = inv_norm[i];
-  for (int d = tid; d < D; d += 256) srow[d] = emb[(size_t)i * D + d] * ni;
+  auto inv_of = [](float sumsq) { return 1.0f / fmaxf(sqrtf(sumsq), 1e-12f); };   // F.normalize eps
+  {
+    float q = 0.f;
+    for (int d = lane; d < D; d += 64) {
+      const float v = emb[(size_t)i * D + d];
+      q = fmaf(v, v, q);
+    }
+    const float ni = inv_of(mst::wave_sum(q));   // (every wave: the same bits)
+    for (int d = tid; d < D; d += kInfoThreads) srow[d] = emb[(size_t)i * D + d] * ni;
+  }
   __syncthreads();
   float* s = sim + (size_t)blockIdx.x * N;
   float mx = -INFINITY;
-  for (int j0 = wave * 4; j0 < N; j0 += 16) {  // one wave = 4 columns at a time: 4 independent coalesced dot products
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int j0 = wave * 4; j0 < N; j0 += 4 * kInfoWaves) {  // one wave = 4 columns at a time: 4 independent coalesced dot products
+    float a[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
     const float* ej[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) ej[u] = emb + (size_t)min(j0 + u, N - 1) * D;
+#pragma unroll 4
     for (int d = lane; d < D; d += 64) {
       const float x = srow[d];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) a[u] = fmaf(x, ej[u][d], a[u]);
+      for (int u = 0; u < 4; ++u) {
+        const float v = ej[u][d];
+        a[u] = fmaf(x, v, a[u]);
+        q[u] = fmaf(v, v, q[u]);
+      }
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int j = j0 + u;
       if (j >= N) break;
-      const float v = mst::wave_sum(a[u]) * inv_norm[j] * inv_tau;
+      const float v = mst::wave_sum(a[u]) * inv_of(mst::wave_sum(q[u])) * inv_tau;
       if (lane == 0) s[j] = v;
       mx = fmaxf(mx, v);
     }
   }
   if (lane == 0) red[wave] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();   // (also orders the lane-0 stores of s[] before the reads below: same workgroup, same L1)
+  mx = red[0];
+#pragma unroll
+  for (int w = 1; w < kInfoWaves; ++w) mx = fmaxf(mx, red[w]);
   const int64_t li = labels[i];
   float pos = 0.f, neg = 0.f;
-  for (int j = tid; j < N; j += 256) {
+  for (int j = tid; j < N; j += kInfoThreads) {
     const float e = expf(s[j] - mx);
     const bool same = labels[j] == li;
     if (same && j != i) pos += e;
     if (!same) neg += e;
   }
   pos = mst::wave_sum(pos), neg = mst::wave_sum(neg);
-  if (lane == 0) red[4 + wave] = pos, red[8 + wave] = neg;
+  if (lane == 0) red[kInfoWaves + wave] = pos, red[2 * kInfoWaves + wave] = neg;
   __syncthreads();
   if (tid == 0) {
-    pos = (red[4] + red[5]) + (red[6] + red[7]);
-    neg = (red[8] + red[9]) + (red[10] + red[11]);
-    // per-row result; summed in a fixed order by infonce_reduce_kernel (no float atomics: the loss value is bit-identical
-    // from run to run, as the reference's deterministic mode asks -- src/train.py:30)
+    pos = neg = 0.f;
+#pragma unroll
+    for (int w = 0; w < kInfoWaves; ++w) pos += red[kInfoWaves + w], neg += red[2 * kInfoWaves + w];
     rowout[2 * blockIdx.x] = pos > 0.f ? -logf(pos / (pos + neg + 1e-8f)) : 0.f;
     rowout[2 * blockIdx.x + 1] = pos > 0.f ? 1.0f : 0.f;
   }
@@ -197,12 +220,11 @@ int mst_infonce_forward(const float* emb, const int64_t* labels, int N, int D, i
   if (!workspace || workspace_bytes < need)
     return mst::fail(MST_ENOMEM, "mst_infonce_forward: workspace %zu B < required %zu B", workspace_bytes, need);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  float* inv_norm = reinterpret_cast<float*>(workspace);
+  // (the workspace's first region, N floats, holds the inverse norms of the backward pass; the forward forms its own in registers)
   float* sim = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + mst::align_up((size_t)N * sizeof(float), 256));
   float* rowout = reinterpret_cast<float*>(reinterpret_cast<char*>(sim) + mst::align_up((size_t)N * N * sizeof(float), 256));
-  hipLaunchKernelGGL(l2norm_kernel, dim3(N), dim3(256), 0, st, emb, inv_norm, D);
-  hipLaunchKernelGGL(infonce_rows_kernel, dim3(rows), dim3(256), (size_t)D * sizeof(float), st, emb, labels, inv_norm, sim,
-                     N, D, row0, 1.0f / temperature, rowout);
+  hipLaunchKernelGGL(infonce_fwd_kernel, dim3(rows), dim3(kInfoThreads), (size_t)D * sizeof(float), st, emb, labels, sim, N, D, row0,
+                     1.0f / temperature, rowout);
   hipLaunchKernelGGL(infonce_reduce_kernel, dim3(1), dim3(256), 0, st, rowout, rows, out);
   MST_HIP_CHECK(hipGetLastError());
   return MST_OK;

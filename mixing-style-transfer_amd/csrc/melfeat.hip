@@ -869,16 +869,25 @@ struct FParams {
   int M, F, T, runs_per_clip, pstride, detailed_bins, feat_dim;
 };
 
-__device__ double pearson_vs_index(const double* y, int n) {
+// fp64 sum over the 64 lanes of a wave: a fixed butterfly, every lane ends with the same bits
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// one wave: lane l takes y[l], y[l + 64], ...; the lanes' partial sums meet in wave_sum_f64's tree
+__device__ double pearson_vs_index(const double* y, int n, int lane) {
   double my = 0;
-  for (int i = 0; i < n; ++i) my += y[i];
-  my /= n;
+  for (int i = lane; i < n; i += 64) my += y[i];
+  my = wave_sum_f64(my) / n;
   const double mx = 0.5 * (n - 1);
   double sxy = 0, sxx = 0, syy = 0;
-  for (int i = 0; i < n; ++i) {
+  for (int i = lane; i < n; i += 64) {
     const double dx = i - mx, dy = y[i] - my;
     sxy += dx * dy, sxx += dx * dx, syy += dy * dy;
   }
+  sxy = wave_sum_f64(sxy), sxx = wave_sum_f64(sxx), syy = wave_sum_f64(syy);
   const double std_unbiased = sqrt(syy / (n - 1));
   if (std_unbiased < 1e-6) return 0.0;  // mixing_utils.py:184
   double c = sxy / sqrt(sxx * syy);
@@ -949,16 +958,20 @@ __global__ __launch_bounds__(256) void melfeat_finalize_kernel(const FParams p) 
   const int sd = p.detailed_bins > 0 ? p.detailed_bins + 2 : 5;
   const int ps = 10 + sd;  // dynamics 6 + rel_loudness 1 + spectral + stereo 3
   float* out = p.feats + (size_t)clip * p.feat_dim;
-  auto put = [&](int idx, double v) {
+  const int lane = tid & 63;
+  auto put_lane = [&](int idx, double v) {
     float f = (float)v;
     f = fminf(fmaxf(f, -100.0f), 100.0f);  // clamp; fminf/fmaxf drop NaN like the NaN->0 step below
     if (v != v) f = 0.0f;                  // NaN -> 0 (mixing_utils.py:343-348)
     out[idx] = f;
   };
+  auto put = [&](int idx, double v) {   // a value every lane of the wave holds: lane 0 stores it
+    if (lane == 0) put_lane(idx, v);
+  };
   const double n = (double)p.T;
   auto loud = [&](double ms) { return -0.691 + 10.0 * log10(ms + 1e-10); };
-  if (tid < 4) {
-    const int s = tid;  // stem index in input order v,b,d,o ; sorted-key block order b,d,(mask),o,v
+  {   // one wave per stem (the block has 4 waves): the sums over the bands are spread over its lanes
+    const int s = tid >> 6;  // stem index in input order v,b,d,o ; sorted-key block order b,d,(mask),o,v
     const int blk = (s == 1) ? 0 : (s == 2) ? ps : (s == 3) ? 2 * ps + 4 : 3 * ps + 4;
     const double msL = sc[S_SQ + 2 * s] / n, msR = sc[S_SQ + 2 * s + 1] / n;
     const double rmsL = sqrt(msL), rmsR = sqrt(msR);
@@ -980,18 +993,19 @@ __global__ __launch_bounds__(256) void melfeat_finalize_kernel(const FParams p) 
     if (p.detailed_bins == 0) {
       const int q = M / 4;
       double lo = 0, mi = 0, hi = 0;
-      for (int i = 0; i < q; ++i) lo += e[i];
-      for (int i = q; i < 3 * q; ++i) mi += e[i];
-      for (int i = 3 * q; i < M; ++i) hi += e[i];
+      for (int i = lane; i < q; i += 64) lo += e[i];
+      for (int i = q + lane; i < 3 * q; i += 64) mi += e[i];
+      for (int i = 3 * q + lane; i < M; i += 64) hi += e[i];
+      lo = wave_sum_f64(lo), mi = wave_sum_f64(mi), hi = wave_sum_f64(hi);
       put(o + 0, lo / q);
       put(o + 1, mi / (2 * q));
       put(o + 2, hi / (M - 3 * q));
-      put(o + 3, pearson_vs_index(e, M));
+      put(o + 3, pearson_vs_index(e, M, lane));
       put(o + 4, flat);
     } else {
       const int nb = p.detailed_bins;
       double* curve = reinterpret_cast<double*>(smem) + 4 * M + kNumScalars + 24 + s * nb;
-      for (int i = 0; i < nb; ++i) {
+      for (int i = lane; i < nb; i += 64) {
         if (nb >= M) { curve[i] = e[i]; continue; }
         const float scale = nb > 1 ? (float)(M - 1) / (float)(nb - 1) : 0.f;  // align_corners=True
         const float src = scale * i;
@@ -1001,8 +1015,9 @@ __global__ __launch_bounds__(256) void melfeat_finalize_kernel(const FParams p) 
         const double lam = src - (float)i0;
         curve[i] = (1.0 - lam) * e[i0] + lam * e[i1];
       }
-      for (int i = 0; i < nb; ++i) put(o + i, curve[i]);
-      put(o + nb, pearson_vs_index(curve, nb));
+      __syncthreads();   // (uniform: every thread of the block takes this branch)
+      for (int i = lane; i < nb; i += 64) put_lane(o + i, curve[i]);
+      put(o + nb, pearson_vs_index(curve, nb, lane));
       put(o + nb + 1, flat);
     }
     o = blk + 7 + sd;
