@@ -437,6 +437,38 @@ int mst_film_backward(const mst_film_dims* dims, const mst_film_weights* w, cons
                       const float* dfilm, const void* save, const mst_film_grads* grads, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* Song-identity discriminator of the adversarial branch = SongIdentityDiscriminator.forward (src/model.py:545-587):
+ * h1 = Dropout(ReLU(w0 x + b0));  h2 = Dropout(ReLU(w3 h1 + b3));  pred = w6 h2 + b6.   x: dev [B][in_dim];  pred: dev [B][out_dim].
+ * Both Dropouts use drop_p (0 = eval mode / no dropout); the keep decision of element m * hidden + n of h1 / h2 is that of
+ * mst_dropout_mask under seed1 / seed2.  `save` (mst_disc_save_bytes) carries the activations to the backward; NULL when no
+ * backward will follow (a row-per-workgroup kernel then computes the same function without any scratch).
+ * mst_disc_backward: dpred [B][out_dim] -> the six parameter gradients (overwritten) and dx [B][in_dim]; dx == NULL skips the
+ * input gradient (a caller that trains the discriminator alone).  Every dimension 1..2048, B >= 1.                          */
+typedef struct mst_disc_dims { int32_t in_dim, hidden, out_dim; } mst_disc_dims;
+typedef struct mst_disc_weights {
+  const float *w0, *b0;   /* network.0 [H][in_dim], [H] */
+  const float *w3, *b3;   /* network.3 [H][H], [H]      */
+  const float *w6, *b6;   /* network.6 [O][H], [O]      */
+} mst_disc_weights;
+typedef struct mst_disc_grads { float *w0, *b0, *w3, *b3, *w6, *b6; } mst_disc_grads;
+size_t mst_disc_save_bytes(const mst_disc_dims* dims, int B);
+size_t mst_disc_backward_workspace_bytes(const mst_disc_dims* dims, int B);
+int mst_disc_forward(const mst_disc_dims* dims, const mst_disc_weights* w, const float* x, int B, float drop_p, uint64_t seed1,
+                     uint64_t seed2, float* pred, void* save, size_t save_bytes, void* stream);
+int mst_disc_backward(const mst_disc_dims* dims, const mst_disc_weights* w, const float* x, int B, float drop_p, uint64_t seed1,
+                      uint64_t seed2, const float* dpred, const void* save, const mst_disc_grads* grads, float* dx,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* Cosine-distance loss of the adversarial branch (src/train.py:199-202):
+ * loss = mean_i (1 - p_i . t_i / (max(|p_i|, 1e-12) max(|t_i|, 1e-12))).   pred, target: dev [K][D], K >= 1, 1 <= D <= 2048.
+ * loss: dev [1];  save: dev [K][3] = (p.p, t.t, p.t) per row, taken back by the backward.  Rows are summed in index order by
+ * one workgroup: bit-reproducible, no host synchronisation.
+ * mst_cosdist_backward: dpred [K][D] = dloss * d loss / d pred with F.normalize's clamp (a row with |p_i| <= 1e-12 gets
+ * -(dloss / K) t^_i / 1e-12; an all-zero target row gets zeros); dloss: dev [1].  The target gets no gradient.              */
+int mst_cosdist_forward(const float* pred, const float* target, int K, int D, float* loss, float* save, void* stream);
+int mst_cosdist_backward(const float* pred, const float* target, int K, int D, const float* save, const float* dloss,
+                         float* dpred, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * InfoNCE forward on (gathered) embeddings.  Replaces InfoNCELoss.forward src/loss.py:31-136.
  * emb: dev [N][D] fp32; labels: dev [N] int64; anchors [row0,row0+rows) are the local rows.

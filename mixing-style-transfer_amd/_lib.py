@@ -86,6 +86,14 @@ class FilmPtrs(C.Structure):   # mst_film_weights / mst_film_grads
     _fields_ = [(k, C.c_void_p) for k in ("mlp0_w", "mlp0_b", "mlp3_w", "mlp3_b", "head_w", "head_b")]
 
 
+class DiscDims(C.Structure):
+    _fields_ = [("in_dim", C.c_int32), ("hidden", C.c_int32), ("out_dim", C.c_int32)]
+
+
+class DiscPtrs(C.Structure):   # mst_disc_weights / mst_disc_grads
+    _fields_ = [(k, C.c_void_p) for k in ("w0", "b0", "w3", "b3", "w6", "b6")]
+
+
 class TcnConfig(C.Structure):
     _fields_ = [("in_channels", C.c_int32), ("hidden_channels", C.c_int32), ("num_blocks", C.c_int32),
                 ("kernel_size", C.c_int32), ("causal", C.c_int32), ("use_film", C.c_int32), ("bn_eps", C.c_float)]
@@ -150,6 +158,14 @@ SYMBOLS = {
                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mst_film_backward": (C.c_int, [C.POINTER(FilmDims), C.POINTER(FilmPtrs), C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                     C.POINTER(FilmPtrs), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mst_disc_save_bytes": (C.c_size_t, [C.POINTER(DiscDims), C.c_int]),
+    "mst_disc_backward_workspace_bytes": (C.c_size_t, [C.POINTER(DiscDims), C.c_int]),
+    "mst_disc_forward": (C.c_int, [C.POINTER(DiscDims), C.POINTER(DiscPtrs), C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_uint64,
+                                   C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mst_disc_backward": (C.c_int, [C.POINTER(DiscDims), C.POINTER(DiscPtrs), C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_uint64,
+                                    C.c_void_p, C.c_void_p, C.POINTER(DiscPtrs), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mst_cosdist_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mst_cosdist_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mst_encoder_train_update_running_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                          C.c_float, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mst_encoder_update_params": (C.c_int, [C.c_void_p, C.POINTER(EncoderWeights), C.c_void_p]),

@@ -4,6 +4,7 @@
 //       emb = Dropout(ReLU(Wp pooled + bp))
 //   * the FiLM MLP, reference src/model.py:385-464 --
 //       h1 = Dropout(ReLU(W1 f + b1));  h2 = ReLU(W3 h1 + b3);  film = Wh h2 + bh
+//   * (at the end of the file) the song-identity discriminator and the cosine-distance loss of the adversarial branch
 // with the gradients autograd derives from them.  fp32 throughout (products on v_mfma_f32_16x16x4_f32 where a GEMM is large
 // enough to matter, fp32 FMA chains elsewhere); every reduction has a fixed order (no atomics): bit-deterministic.
 // Dropout masks are never stored: a keep decision is a pure function of (seed, element index) (Philox-2x32-10, common.h) and
@@ -539,6 +540,231 @@ int mst_film_backward(const mst_film_dims* dm, const mst_film_weights* w, const 
   hipLaunchKernelGGL(colsum_kernel, dim3((H + 63) / 64), blk, 0, st, dh1, g->mlp0_b, B, H);
   hipLaunchKernelGGL((gemm_kernel<true, true, ColMajA, RowMajB, EpiStore>), dim3((Fd + 63) / 64, (H + 63) / 64, 1), blk, 0, st, H, Fd, B, 1,
                      round_up(B, kKC), ColMajA{dh1, H}, RowMajB{feats, Fd}, EpiStore{g->mlp0_w, Fd});
+  MST_HIP_CHECK(hipGetLastError());
+  return MST_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Song-identity discriminator of the adversarial branch (reference src/model.py:545-587) --
+//     h1 = Dropout(ReLU(W0 x + b0));  h2 = Dropout(ReLU(W3 h1 + b3));  pred = W6 h2 + b6
+// -- and the cosine-distance loss it is trained with (src/train.py:199-202).  The same GEMM kernel as above, every product
+// split-K (the M x N tile grids of these shapes are 8 to 48 workgroups) with the bias / ReLU / Dropout epilogue in the finish
+// kernel; the input of this network is the embedding, so the backward also returns dx.
+// ------------------------------------------------------------------------------------------
+namespace {
+constexpr int kSplitDisc = kSplitFilm;
+constexpr int kDiscMaxDim = 2048, kDiscMaxRows = 1 << 20;
+struct FinLin {   // out[m][n] = Dropout(act(sum + bias[n])), element index m * N + n
+  float* out; const float* bias; int N, relu; Drop d;
+  __device__ void operator()(long long i, float v) const {
+    float x = v + bias[i % N];
+    if (relu) x = x < 0.f ? 0.f : x;   // (keeps NaN)
+    out[i] = drop_apply(d, (size_t)i, x);
+  }
+};
+struct DiscSave {   // offsets (floats): the two dropped activations, then the forward's split-K partial sums
+  size_t h1, h2, part, total;
+};
+DiscSave disc_save(int B, int H, int O) {
+  DiscSave s{};
+  s.h1 = 0, s.h2 = (size_t)B * H, s.part = 2 * (size_t)B * H;
+  s.total = s.part + (size_t)kSplitDisc * B * std::max(H, O);
+  return s;
+}
+struct DiscWork {   // backward scratch: dh2, dh1, split-K partial sums
+  size_t dh2, dh1, part, total;
+};
+DiscWork disc_work(int B, int I, int H) {
+  DiscWork s{};
+  s.dh2 = 0, s.dh1 = (size_t)B * H, s.part = 2 * (size_t)B * H;
+  s.total = s.part + (size_t)kSplitDisc * B * std::max(H, I);
+  return s;
+}
+bool disc_dims_ok(const mst_disc_dims* d) {
+  return d->in_dim >= 1 && d->in_dim <= kDiscMaxDim && d->hidden >= 1 && d->hidden <= kDiscMaxDim && d->out_dim >= 1 &&
+         d->out_dim <= kDiscMaxDim;
+}
+
+// The forward without a save buffer (no backward will follow, nowhere to keep the activations): block = one row, the three
+// layers back to back with x, h1 and h2 in LDS; a wave per output unit, lanes over the input units (consecutive addresses of
+// the weight row), fixed-order wave sum.  The same Dropout decisions as the GEMM path; sums in another order.
+// disc_row_layer: out[n] = Dropout(act(W[n] . in + bias[n])) of row m.
+__device__ __forceinline__ void disc_row_layer(const float* in, int K, const float* __restrict__ W, const float* __restrict__ bias, int N,
+                                               float* out, int relu, const Drop& d, int m) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int n = wave; n < N; n += 4) {
+    const float* wr = W + (size_t)n * K;
+    float s = 0.f;
+    for (int k = lane; k < K; k += 64) s = fmaf(wr[k], in[k], s);
+    s = mst::wave_sum(s);
+    if (lane == 0) {
+      float v = s + bias[n];
+      if (relu) v = v < 0.f ? 0.f : v;
+      out[n] = drop_apply(d, (size_t)m * N + n, v);
+    }
+  }
+}
+__global__ __launch_bounds__(256) void disc_row_kernel(const float* __restrict__ x, const float* __restrict__ w0, const float* __restrict__ b0,
+                                                       const float* __restrict__ w3, const float* __restrict__ b3, const float* __restrict__ w6,
+                                                       const float* __restrict__ b6, float* __restrict__ pred, int I, int H, int O, Drop d1, Drop d2) {
+  __shared__ float xs[kDiscMaxDim], h1[kDiscMaxDim], h2[kDiscMaxDim];
+  const int m = blockIdx.x;
+  for (int k = threadIdx.x; k < I; k += 256) xs[k] = x[(size_t)m * I + k];
+  __syncthreads();
+  disc_row_layer(xs, I, w0, b0, H, h1, 1, d1, m);
+  __syncthreads();
+  disc_row_layer(h1, H, w3, b3, H, h2, 1, d2, m);
+  __syncthreads();
+  disc_row_layer(h2, H, w6, b6, O, pred + (size_t)m * O, 0, Drop{0ull, 0u, 1.f}, m);
+}
+
+// cosine distance: a wave per row, save[row] = (p . p, t . t, p . t)
+constexpr float kCosEps = 1e-12f;   // F.normalize's clamp
+__global__ __launch_bounds__(256) void cosdist_rows_kernel(const float* __restrict__ pred, const float* __restrict__ target, int K, int D,
+                                                           float* __restrict__ save) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= K) return;
+  const float* p = pred + (size_t)row * D;
+  const float* t = target + (size_t)row * D;
+  float pp = 0.f, tt = 0.f, pt = 0.f;
+  for (int k = lane; k < D; k += 64) {
+    const float a = p[k], b = t[k];
+    pp = fmaf(a, a, pp), tt = fmaf(b, b, tt), pt = fmaf(a, b, pt);
+  }
+  pp = mst::wave_sum(pp), tt = mst::wave_sum(tt), pt = mst::wave_sum(pt);
+  if (lane == 0) save[(size_t)3 * row] = pp, save[(size_t)3 * row + 1] = tt, save[(size_t)3 * row + 2] = pt;
+}
+// one workgroup: thread i sums its run of consecutive rows in index order, thread 0 the 256 run sums in thread order.  The K row
+// terms and their sum are formed in double and rounded once (K divisions and square roots in all: the loss then carries the
+// rounding of the fp32 dot products and one final rounding, not K more on top)
+__device__ __forceinline__ double cosdist_row_loss(const float* s) {
+  return 1.0 - (double)s[2] / (fmax(sqrt((double)s[0]), (double)kCosEps) * fmax(sqrt((double)s[1]), (double)kCosEps));
+}
+__global__ __launch_bounds__(256) void cosdist_mean_kernel(const float* __restrict__ save, int K, float* __restrict__ loss) {
+  __shared__ double part[256];
+  const int tid = threadIdx.x, per = (K + 255) / 256, r0 = tid * per, r1 = min(K, r0 + per);
+  double s = 0.0;
+  for (int r = r0; r < r1; ++r) s += cosdist_row_loss(save + (size_t)3 * r);
+  part[tid] = s;
+  __syncthreads();
+  if (tid == 0) {
+    double tot = 0.0;
+    for (int i = 0; i < 256; ++i) tot += part[i];
+    loss[0] = (float)(tot / (double)K);
+  }
+}
+// dpred_i = -(dloss / K) (t^_i - cos_i p^_i) / |p_i|   (|p_i| > eps; else -(dloss / K) t^_i / eps): a wave per row
+__global__ __launch_bounds__(256) void cosdist_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ target, int K, int D,
+                                                          const float* __restrict__ save, const float* __restrict__ dloss,
+                                                          float* __restrict__ dpred) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= K) return;
+  const float* s = save + (size_t)3 * row;
+  const float np = sqrtf(s[0]), nt = fmaxf(sqrtf(s[1]), kCosEps), g = -dloss[0] / (float)K;
+  const float* p = pred + (size_t)row * D;
+  const float* t = target + (size_t)row * D;
+  float* o = dpred + (size_t)row * D;
+  if (np > kCosEps) {
+    const float inp = 1.f / np, cs = s[2] / (np * nt);
+    for (int k = lane; k < D; k += 64) o[k] = g * (t[k] / nt - cs * (p[k] * inp)) * inp;
+  } else {
+    for (int k = lane; k < D; k += 64) o[k] = g * (t[k] / nt) / kCosEps;
+  }
+}
+}  // namespace
+
+extern "C" {
+
+size_t mst_disc_save_bytes(const mst_disc_dims* d, int B) {
+  if (!d || B <= 0 || B > kDiscMaxRows || !disc_dims_ok(d)) return 0;
+  return disc_save(B, d->hidden, d->out_dim).total * sizeof(float);
+}
+size_t mst_disc_backward_workspace_bytes(const mst_disc_dims* d, int B) {
+  if (!d || B <= 0 || B > kDiscMaxRows || !disc_dims_ok(d)) return 0;
+  return disc_work(B, d->in_dim, d->hidden).total * sizeof(float);
+}
+
+int mst_disc_forward(const mst_disc_dims* dm, const mst_disc_weights* w, const float* x, int B, float drop_p, uint64_t seed1,
+                     uint64_t seed2, float* pred, void* save, size_t save_bytes, void* stream) {
+  MST_REQUIRE(dm && w && x && pred, "mst_disc_forward: NULL argument");
+  MST_REQUIRE(w->w0 && w->b0 && w->w3 && w->b3 && w->w6 && w->b6, "mst_disc_forward: NULL weight");
+  MST_REQUIRE(disc_dims_ok(dm), "mst_disc_forward: dims out of range (in_dim=%d hidden=%d out_dim=%d; each must be in 1..%d)", dm->in_dim,
+              dm->hidden, dm->out_dim, kDiscMaxDim);
+  MST_REQUIRE(B >= 1 && B <= kDiscMaxRows, "mst_disc_forward: B=%d rows, must be in 1..%d", B, kDiscMaxRows);
+  MST_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "mst_disc_forward: dropout p must be in [0, 1)");
+  const int I = dm->in_dim, H = dm->hidden, O = dm->out_dim;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const Drop d1 = make_drop(drop_p, seed1), d2 = make_drop(drop_p, seed2), d0 = make_drop(0.f, 0);
+  if (!save) {
+    hipLaunchKernelGGL(disc_row_kernel, dim3(B), dim3(256), 0, st, x, w->w0, w->b0, w->w3, w->b3, w->w6, w->b6, pred, I, H, O, d1, d2);
+    MST_HIP_CHECK(hipGetLastError());
+    return MST_OK;
+  }
+  const DiscSave S = disc_save(B, H, O);
+  if (save_bytes < S.total * sizeof(float)) return mst::fail(MST_ENOMEM, "mst_disc_forward: save buffer %zu B < %zu B", save_bytes, S.total * sizeof(float));
+  float* sv = static_cast<float*>(save);
+  gemm_split<false, false>(B, H, I, kSplitDisc, RowMajA{x, I}, RowMajT{w->w0, I}, sv + S.part, FinLin{sv + S.h1, w->b0, H, 1, d1}, st);
+  gemm_split<false, false>(B, H, H, kSplitDisc, RowMajA{sv + S.h1, H}, RowMajT{w->w3, H}, sv + S.part, FinLin{sv + S.h2, w->b3, H, 1, d2}, st);
+  gemm_split<false, false>(B, O, H, kSplitDisc, RowMajA{sv + S.h2, H}, RowMajT{w->w6, H}, sv + S.part, FinLin{pred, w->b6, O, 0, d0}, st);
+  MST_HIP_CHECK(hipGetLastError());
+  return MST_OK;
+}
+
+int mst_disc_backward(const mst_disc_dims* dm, const mst_disc_weights* w, const float* x, int B, float drop_p, uint64_t seed1,
+                      uint64_t seed2, const float* dpred, const void* save, const mst_disc_grads* g, float* dx, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+  (void)seed1, (void)seed2;   // the survivors of a Dropout behind a ReLU are exactly the positive entries of the saved activation
+  MST_REQUIRE(dm && w && x && dpred && save && g && workspace, "mst_disc_backward: NULL argument");
+  MST_REQUIRE(w->w0 && w->b0 && w->w3 && w->b3 && w->w6 && w->b6, "mst_disc_backward: NULL weight");
+  MST_REQUIRE(g->w0 && g->b0 && g->w3 && g->b3 && g->w6 && g->b6, "mst_disc_backward: NULL gradient pointer");
+  MST_REQUIRE(disc_dims_ok(dm), "mst_disc_backward: dims out of range (in_dim=%d hidden=%d out_dim=%d; each must be in 1..%d)", dm->in_dim,
+              dm->hidden, dm->out_dim, kDiscMaxDim);
+  MST_REQUIRE(B >= 1 && B <= kDiscMaxRows, "mst_disc_backward: B=%d rows, must be in 1..%d", B, kDiscMaxRows);
+  MST_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "mst_disc_backward: dropout p must be in [0, 1)");
+  const int I = dm->in_dim, H = dm->hidden, O = dm->out_dim;
+  const DiscSave S = disc_save(B, H, O);
+  const DiscWork Wk = disc_work(B, I, H);
+  if (workspace_bytes < Wk.total * sizeof(float)) return mst::fail(MST_ENOMEM, "mst_disc_backward: workspace %zu B < %zu B", workspace_bytes, Wk.total * sizeof(float));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const float* sv = static_cast<const float*>(save);
+  const float *h1 = sv + S.h1, *h2 = sv + S.h2;
+  float* ws = static_cast<float*>(workspace);
+  float *dh2 = ws + Wk.dh2, *dh1 = ws + Wk.dh1, *part = ws + Wk.part;
+  const float gscale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+  const dim3 blk(256);
+  auto wgrad = [&](const float* dy, int N, const float* in, int K, float* dw, float* db) {   // db = colsum(dy), dw = dy^T in
+    hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64), blk, 0, st, dy, db, B, N);
+    hipLaunchKernelGGL((gemm_kernel<true, true, ColMajA, RowMajB, EpiStore>), dim3((K + 63) / 64, (N + 63) / 64, 1), blk, 0, st, N, K, B, 1,
+                       round_up(B, kKC), ColMajA{dy, N}, RowMajB{in, K}, EpiStore{dw, K});
+  };
+  wgrad(dpred, O, h2, H, g->w6, g->b6);
+  gemm_split<false, true>(B, H, O, kSplitDisc, RowMajA{dpred, O}, RowMajB{w->w6, H}, part, FinMask{dh2, h2, gscale}, st);
+  wgrad(dh2, H, h1, H, g->w3, g->b3);
+  gemm_split<false, true>(B, H, H, kSplitDisc, RowMajA{dh2, H}, RowMajB{w->w3, H}, part, FinMask{dh1, h1, gscale}, st);
+  wgrad(dh1, H, x, I, g->w0, g->b0);
+  if (dx) gemm_split<false, true>(B, I, H, kSplitDisc, RowMajA{dh1, H}, RowMajB{w->w0, I}, part, FinStore{dx}, st);
+  MST_HIP_CHECK(hipGetLastError());
+  return MST_OK;
+}
+
+int mst_cosdist_forward(const float* pred, const float* target, int K, int D, float* loss, float* save, void* stream) {
+  MST_REQUIRE(pred && target && loss && save, "mst_cosdist_forward: NULL argument");
+  MST_REQUIRE(K >= 1 && D >= 1 && D <= kDiscMaxDim, "mst_cosdist_forward: K=%d rows, D=%d (K >= 1, 1 <= D <= %d)", K, D, kDiscMaxDim);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(cosdist_rows_kernel, dim3((K + 3) / 4), dim3(256), 0, st, pred, target, K, D, save);
+  hipLaunchKernelGGL(cosdist_mean_kernel, dim3(1), dim3(256), 0, st, save, K, loss);
+  MST_HIP_CHECK(hipGetLastError());
+  return MST_OK;
+}
+
+int mst_cosdist_backward(const float* pred, const float* target, int K, int D, const float* save, const float* dloss, float* dpred,
+                         void* stream) {
+  MST_REQUIRE(pred && target && save && dloss && dpred, "mst_cosdist_backward: NULL argument");
+  MST_REQUIRE(K >= 1 && D >= 1 && D <= kDiscMaxDim, "mst_cosdist_backward: K=%d rows, D=%d (K >= 1, 1 <= D <= %d)", K, D, kDiscMaxDim);
+  hipLaunchKernelGGL(cosdist_bwd_kernel, dim3((K + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pred, target, K, D, save,
+                     dloss, dpred);
   MST_HIP_CHECK(hipGetLastError());
   return MST_OK;
 }

@@ -378,3 +378,63 @@ class MultiResolutionSTFTLoss(nn.Module):
             else:
                 total_loss += self.sc_weight * sc_loss + self.log_weight * log_mag_loss
         return total_loss / len(self.fft_sizes)
+
+
+class _CosDistHip(torch.autograd.Function):
+    """mean_i (1 - cos(pred_i, target_i)) in libmst.so (`mst_cosdist_forward` / `mst_cosdist_backward`); gradient to `pred` only."""
+
+    @staticmethod
+    def forward(ctx, pred, target):
+        from . import _lib
+        p, t = pred.detach().contiguous(), target.detach().contiguous()
+        K, D = p.shape
+        loss = torch.empty(1, dtype=torch.float32, device=p.device)
+        save = torch.empty(K, 3, dtype=torch.float32, device=p.device)
+        with torch.cuda.device(p.device):
+            _lib.check(_lib.lib().mst_cosdist_forward(_lib.dptr(p), _lib.dptr(t), K, D, _lib.dptr(loss), _lib.dptr(save),
+                                                      _lib.stream_ptr(p.device)), "mst_cosdist_forward")
+        ctx.save_for_backward(p, t, save)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        from . import _lib
+        p, t, save = ctx.saved_tensors
+        K, D = p.shape
+        grad = torch.empty_like(p)
+        g = g_loss.detach().reshape(1).float().contiguous()
+        with torch.cuda.device(p.device):
+            _lib.check(_lib.lib().mst_cosdist_backward(_lib.dptr(p), _lib.dptr(t), K, D, _lib.dptr(save), _lib.dptr(g), _lib.dptr(grad),
+                                                       _lib.stream_ptr(p.device)), "mst_cosdist_backward")
+        return grad, None
+
+
+def cosine_distance_loss(pred, target, backend="hip"):
+    """The adversarial branch's loss (reference src/train.py:199-202): mean over rows of 1 - cosine similarity of `pred` and
+    `target` (K, D), both normalised as F.normalize does (norm clamped at 1e-12).  `backend="hip"`: forward and the gradient to
+    `pred` in libmst.so (fp32 CUDA tensors, D <= 2048, `target` without gradient; anything else raises, naming the reason);
+    `backend="torch"`: the reference's three lines on PyTorch ops (any device, dtype, autograd to both arguments)."""
+    if backend not in ("hip", "torch"):
+        raise ValueError("backend must be 'hip' or 'torch'")
+    if backend == "torch":
+        pred_norm = F.normalize(pred, dim=1)
+        target_norm = F.normalize(target, dim=1)
+        return (1.0 - (pred_norm * target_norm).sum(dim=1)).mean()
+    why = None
+    for name, t in (("pred", pred), ("target", target)):
+        if not t.is_cuda:
+            why = f"the HIP backend needs CUDA tensors (there is no CPU fallback), got {name} on {t.device}"
+        elif t.dtype != torch.float32:
+            why = f"the HIP backend is fp32, got {name} of {t.dtype}"
+        if why:
+            break
+    if why is None:
+        if pred.dim() != 2 or pred.shape != target.shape or pred.device != target.device:
+            why = f"the HIP backend needs pred and target of one shape (K, D) on one device, got {tuple(pred.shape)} and {tuple(target.shape)}"
+        elif pred.shape[0] < 1 or not 1 <= pred.shape[1] <= 2048:
+            why = f"the HIP backend takes K >= 1 rows of 1 <= D <= 2048, got {tuple(pred.shape)}"
+        elif torch.is_grad_enabled() and target.requires_grad:
+            why = "the HIP backend has no gradient to the target (detach it)"
+    if why:
+        raise RuntimeError("cosine_distance_loss: " + why + "; backend='torch' runs the same loss on PyTorch ops")
+    return _CosDistHip.apply(pred, target)

@@ -756,6 +756,47 @@ class _HipFilmMLP(torch.autograd.Function):
         return (None, None) + tuple(grads)
 
 
+class _HipDiscriminator(torch.autograd.Function):
+    """SongIdentityDiscriminator's network (src/model.py:545-587) for training and evaluation, forward and backward in libmst.so
+    (`mst_disc_forward` / `mst_disc_backward`, csrc/head.hip).  Unlike the FiLM MLP's features, the input is the embedding and
+    gets its gradient -- that gradient, reversed, is what the adversarial branch trains the encoder with."""
+
+    @staticmethod
+    def forward(ctx, x, p, w0, b0, w3, b3, w6, b6):
+        f = x.detach().contiguous().float()
+        B = f.shape[0]
+        ws = [t.detach().contiguous().float() for t in (w0, b0, w3, b3, w6, b6)]
+        dims = _lib.DiscDims(ws[0].shape[1], ws[0].shape[0], ws[4].shape[0])
+        L = _lib.lib()
+        seeds = (_seed64(), _seed64()) if p > 0.0 else (0, 0)
+        save = torch.empty(L.mst_disc_save_bytes(C.byref(dims), B), dtype=torch.uint8, device=f.device)
+        pred = torch.empty(B, ws[4].shape[0], device=f.device)
+        wp = _lib.DiscPtrs(*[t.data_ptr() for t in ws])
+        with torch.cuda.device(f.device):
+            _lib.check(L.mst_disc_forward(C.byref(dims), C.byref(wp), _lib.dptr(f), B, float(p), seeds[0], seeds[1], _lib.dptr(pred),
+                                          _lib.dptr(save), save.numel(), _lib.stream_ptr(f.device)), "mst_disc_forward")
+        ctx.cfg = (dims, float(p), seeds)
+        ctx.save_for_backward(f, save, *ws)
+        return pred
+
+    @staticmethod
+    def backward(ctx, dpred):
+        f, save, *ws = ctx.saved_tensors
+        dims, p, seeds = ctx.cfg
+        B = f.shape[0]
+        L = _lib.lib()
+        grads = [torch.empty_like(t) for t in ws]
+        dx = torch.empty_like(f) if ctx.needs_input_grad[0] else None   # (a detached input: the discriminator trains alone)
+        work = torch.empty(L.mst_disc_backward_workspace_bytes(C.byref(dims), B), dtype=torch.uint8, device=f.device)
+        dp = dpred.contiguous().float()
+        wp, gp = _lib.DiscPtrs(*[t.data_ptr() for t in ws]), _lib.DiscPtrs(*[t.data_ptr() for t in grads])
+        with torch.cuda.device(f.device):
+            _lib.check(L.mst_disc_backward(C.byref(dims), C.byref(wp), _lib.dptr(f), B, p, seeds[0], seeds[1], _lib.dptr(dp),
+                                           _lib.dptr(save), C.byref(gp), _lib.dptr(dx), _lib.dptr(work), work.numel(),
+                                           _lib.stream_ptr(f.device)), "mst_disc_backward")
+        return (dx, None) + tuple(grads)
+
+
 class MixingStyleEncoder(nn.Module):
     """reference src/model.py:467-542.  `encoder_backend`: "hip" (default; eval/no-grad forward in libmst.so) or
     "torch" (PyTorch-ROCm ops for stage B; stage A stays HIP) -- BASELINE.json configs[2] vs configs[1]."""
@@ -1051,3 +1092,57 @@ class MixingStyleEncoder(nn.Module):
             raise ValueError(f"mixing_features holds deferred placeholder rows but feature_dim={self.film_encoder.feature_dim} "
                              "is not a MixingFeatureExtractor layout")
         return self.forward_from_logmel(logmel, mf)
+
+
+class SongIdentityDiscriminator(nn.Module):
+    """reference src/model.py:545-587: the MLP that predicts a song-identity embedding from a mixing embedding, trained behind a
+    gradient-reversal layer (mst_amd.grl) so that the encoder learns to hide the song.  Same constructor, `network` Sequential
+    and state_dict keys (`network.0.weight` ... `network.6.bias`): a reference checkpoint's `discriminator_state_dict` loads
+    with strict=True.
+
+    `backend`: "hip" (default) = forward and backward in libmst.so (see _HipDiscriminator) for fp32 CUDA input; a call it cannot
+    take raises RuntimeError naming the reason.  "torch" = explicit opt-in, `self.network` on PyTorch ops (any device, dtype).
+    Inside `torch.autocast` the module runs `self.network` (as the FiLM MLP and the pooling head do: src/train.py:246-296 calls
+    it there with half-precision embeddings)."""
+
+    backend = "hip"
+
+    def __init__(self, input_dim=512, hidden_dim=512, output_dim=512, dropout=0.3):
+        super().__init__()
+        self.network = nn.Sequential(
+            nn.Linear(input_dim, hidden_dim), nn.ReLU(inplace=True), nn.Dropout(dropout),
+            nn.Linear(hidden_dim, hidden_dim), nn.ReLU(inplace=True), nn.Dropout(dropout),
+            nn.Linear(hidden_dim, output_dim))
+
+    def _hip_refusal(self, x):
+        net = self.network
+        if not x.is_cuda:
+            return f"the HIP backend needs a CUDA tensor (there is no CPU fallback), got the input on {x.device}"
+        if x.dtype != torch.float32:
+            return f"the HIP backend is fp32, got an input of {x.dtype}"
+        for q in self.parameters():
+            if q.dtype != torch.float32 or q.device != x.device:
+                return f"the HIP backend needs fp32 parameters on the input's device, got {q.dtype} on {q.device}"
+        dims = (net[0].in_features, net[0].out_features, net[3].in_features, net[3].out_features, net[6].in_features, net[6].out_features)
+        if max(dims) > 2048:
+            return f"the HIP backend takes dimensions up to 2048, got {dims[0]} -> {dims[1]} -> {dims[5]}"
+        if not (dims[1] == dims[2] == dims[3] == dims[4]):
+            return f"the HIP backend needs one hidden width, got Linear layers {dims[:2]}, {dims[2:4]}, {dims[4:]}"
+        if x.dim() < 1 or x.shape[-1] != dims[0] or x.numel() == 0:
+            return f"input of shape {tuple(x.shape)} for input_dim {dims[0]}"
+        if net[2].p != net[5].p or not 0.0 <= net[2].p < 1.0:
+            return f"the HIP backend draws both Dropouts with one p in [0, 1), got {net[2].p} and {net[5].p}"
+        return None
+
+    def forward(self, x):
+        if self.backend not in ("hip", "torch"):
+            raise ValueError("backend must be 'hip' or 'torch'")
+        if self.backend == "torch" or torch.is_autocast_enabled():
+            return self.network(x)
+        why = self._hip_refusal(x)
+        if why:
+            raise RuntimeError("SongIdentityDiscriminator: " + why + "; backend='torch' runs the same network on PyTorch ops")
+        net = self.network
+        out = _HipDiscriminator.apply(x.reshape(-1, x.shape[-1]), float(net[2].p) if self.training else 0.0, net[0].weight, net[0].bias,
+                                      net[3].weight, net[3].bias, net[6].weight, net[6].bias)
+        return out.view(*x.shape[:-1], out.shape[-1])
