@@ -556,6 +556,47 @@ size_t mst_tcn_film_workspace_bytes(const mst_tcn_film* gen, int B);
 int mst_tcn_film_forward(const mst_tcn_film* gen, const float* emb, int B, float* film, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Stage C, training: the mixer in train() mode and its backward (src/train_style_transfer.py:255-317,
+ * inference/test_tcn_style_transfer.py:84-200 back-propagate through it).  BatchNorm1d uses the batch statistics over
+ * (B, T), biased variance; the whole batch goes through one call.  Exact fp32, fixed summation orders, no float atomics:
+ * two calls on the same input give the same bits.
+ * ------------------------------------------------------------------------------------------ */
+/* Refreshes the handle from DEVICE tensors in the layouts of mst_tcn_weights, on `stream`, without a host copy or
+ * synchronisation.  Two groups, each given whole or left NULL: the parameters (input_*, conv_*, bn_w, bn_b, output_*;
+ * the first such call allocates the training copies) and the running statistics (bn_mean, bn_var; read by
+ * mst_tcn_forward only).  The parameters are required once before the training calls and after every change of one.     */
+int mst_tcn_update_params(mst_tcn* tcn, const mst_tcn_weights* device_weights, void* stream);
+/* 0 (and mst_last_error) when the shape is refused.  The workspace serves the forward and the backward.                 */
+size_t mst_tcn_train_save_bytes(const mst_tcn* tcn, int B, long long T);
+size_t mst_tcn_train_workspace_bytes(const mst_tcn* tcn, int B, long long T);
+/* x, y, film as mst_tcn_forward.  batch_mean, batch_var: dev [num_blocks][2][H], the statistics of norm1 / norm2 of
+ * every block (biased variance; the caller updates the running statistics from them).  save: dev, caller-owned, what the
+ * backward reads ((3 num_blocks + 1) * H_padded * 4 bytes per sample); NULL when no backward follows (same y).          */
+int mst_tcn_forward_train(const mst_tcn* tcn, const float* x, const float* film, int B, long long T, float* y,
+                          float* batch_mean, float* batch_var, void* save, size_t save_bytes, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* dev fp32, the reference's parameter layouts stacked as in mst_tcn_weights; every element is overwritten. */
+typedef struct mst_tcn_grads {
+  float *input_w, *input_b;   /* [H][8][1], [H]                 */
+  float *conv_w, *conv_b;     /* [nb][2][H][H][K], [nb][2][H]   */
+  float *bn_w, *bn_b;         /* [nb][2][H] each                */
+  float *output_w, *output_b; /* [8][H][1], [8]                 */
+} mst_tcn_grads;
+/* dy: dev [B][8][T].  x, film, save: what the forward was given and wrote.  dx: dev [B][8][T] or NULL (skipped).
+ * dfilm: dev [B][num_blocks][4][H] or NULL (must be NULL for a mixer without FiLM).                                     */
+int mst_tcn_backward(const mst_tcn* tcn, const float* dy, const float* x, const float* film, int B, long long T,
+                     const void* save, size_t save_bytes, const mst_tcn_grads* grads, float* dx, float* dfilm,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* Tests: masks dev [2 num_blocks][B][H][T] bytes, 1 where the backward takes LeakyReLU slope 1 (the device function the
+ * backward itself uses), in the order conv1, conv2 of block 0, 1, ...                                                   */
+int mst_tcn_train_masks(const mst_tcn* tcn, const void* save, size_t save_bytes, int B, long long T, unsigned char* masks,
+                        void* stream);
+/* Tests: the two linear kernels of one convolution (block, layer 0 / 1) alone.  du, in, din: dev [B][H][T] in the
+ * reference's layout; din = input gradient of du, dw [H][H][K] = weight gradient of du against the input `in`.          */
+int mst_tcn_train_conv_grads(const mst_tcn* tcn, int block, int layer, const float* du, const float* in, int B, long long T,
+                             float* din, float* dw, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,10 @@ class TcnWeights(C.Structure):
                                           "output_w", "output_b")]
 
 
+class TcnGrads(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("input_w", "input_b", "conv_w", "conv_b", "bn_w", "bn_b", "output_w", "output_b")]
+
+
 class TcnTaps(C.Structure):
     _fields_ = [("n", C.c_int32), ("block", C.c_int32 * 4), ("h", C.c_void_p * 4)]
 
@@ -213,6 +217,16 @@ SYMBOLS = {
     "mst_tcn_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_longlong]),
     "mst_tcn_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.POINTER(TcnTaps),
                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mst_tcn_update_params": (C.c_int, [C.c_void_p, C.POINTER(TcnWeights), C.c_void_p]),
+    "mst_tcn_train_save_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_longlong]),
+    "mst_tcn_train_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_longlong]),
+    "mst_tcn_forward_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mst_tcn_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_size_t,
+                                   C.POINTER(TcnGrads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mst_tcn_train_masks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "mst_tcn_train_conv_grads": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mst_tcn_film_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.POINTER(TcnFilmWeights)]),
     "mst_tcn_film_destroy": (None, [C.c_void_p]),
     "mst_tcn_film_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),

@@ -87,7 +87,8 @@ __device__ __forceinline__ void tcn_conv_tap(f32x4 (&acc)[NO][TT], const float* 
 // sc: [B] x sc_stride floats, S at +0 and C at +HP for this (block, layer).  off0: offset of tap 0 (= -padding).
 // NT = HP / 16 tiles of input / output channels, TT time tiles per wave.  SPLIT = 2 (wide mixers): the four waves of a
 // workgroup are 2 time groups x 2 halves of the output channels, so that the accumulators of a wave fit twice.
-template <int NT, int TT, int SPLIT>
+// RAW (training): no fold, no activation -- out = acc + C (+ res when res != NULL); S and epi are not read.
+template <int NT, int TT, int SPLIT, bool RAW = false>
 __global__ __launch_bounds__(256, 2) void tcn_conv_kernel(const float* __restrict__ in, const float* __restrict__ wsw,
                                                           const float* __restrict__ sc, long long sc_stride, const float* res,
                                                           float* out, int T, int K, int dil, int off0, int epi) {
@@ -130,9 +131,13 @@ __global__ __launch_bounds__(256, 2) void tcn_conv_kernel(const float* __restric
       if (t >= T) continue;
       const size_t at = ((size_t)b * T + t) * HP + c;
       f32x4 v = acc[o][m], r = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (epi != EPI_ACT) r = *reinterpret_cast<const f32x4*>(res + at);
+      if (RAW ? res != nullptr : epi != EPI_ACT) r = *reinterpret_cast<const f32x4*>(res + at);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
+        if (RAW) {
+          v[q] = (v[q] + Cc[q]) + r[q];
+          continue;
+        }
         float z = fmaf(S[q], v[q], Cc[q]);
         if (epi == EPI_RES_THEN_ACT) z += r[q];
         z = leaky(z);
@@ -266,12 +271,12 @@ __global__ __launch_bounds__(256) void tcn_linear_kernel(const float* __restrict
   }
 }
 
-template <int NT, int TT, int SPLIT>
+template <int NT, int TT, int SPLIT, bool RAW = false>
 void launch_conv(const float* in, const float* wsw, const float* sc, long long sc_stride, const float* res, float* out, int B,
                  int T, int K, int dil, int off0, int epi, hipStream_t st) {
   const long long per_block = (4LL / SPLIT) * TT * 16;
   dim3 grid((unsigned)((T + per_block - 1) / per_block), (unsigned)B);
-  hipLaunchKernelGGL((tcn_conv_kernel<NT, TT, SPLIT>), grid, dim3(256), 0, st, in, wsw, sc, sc_stride, res, out, T, K, dil, off0,
+  hipLaunchKernelGGL((tcn_conv_kernel<NT, TT, SPLIT, RAW>), grid, dim3(256), 0, st, in, wsw, sc, sc_stride, res, out, T, K, dil, off0,
                      epi);
 }
 
@@ -290,6 +295,19 @@ conv_fn conv_for(int nt) {
   }
   return nullptr;
 }
+conv_fn conv_raw_for(int nt) {
+  switch (nt) {
+    case 1: return launch_conv<1, 8, 1, true>;
+    case 2: return launch_conv<2, 8, 1, true>;
+    case 3: return launch_conv<3, 4, 1, true>;
+    case 4: return launch_conv<4, 4, 1, true>;
+    case 5: return launch_conv<5, 4, 2, true>;
+    case 6: return launch_conv<6, 4, 2, true>;
+    case 7: return launch_conv<7, 4, 2, true>;
+    case 8: return launch_conv<8, 4, 2, true>;
+  }
+  return nullptr;
+}
 
 }  // namespace
 }  // namespace mst
@@ -298,6 +316,9 @@ struct mst_tcn {
   mst_tcn_config cfg;
   int HP;
   float *wsw, *wi, *bi, *wo, *bo, *cb, *bw, *bb, *bm, *bv;
+  // training only, allocated by the first mst_tcn_update_params: the transposed, tap-reversed weights of the input
+  // gradient in A-fragment order, and [2 nb + 1][2][HP] = (1, conv bias) per convolution, then one entry of zeros
+  float *wswT, *rawsc;
 };
 
 struct mst_tcn_film {
@@ -311,7 +332,7 @@ extern "C" {
 
 void mst_tcn_destroy(mst_tcn* h) {
   if (!h) return;
-  float* p[] = {h->wsw, h->wi, h->bi, h->wo, h->bo, h->cb, h->bw, h->bb, h->bm, h->bv};
+  float* p[] = {h->wsw, h->wi, h->bi, h->wo, h->bo, h->cb, h->bw, h->bb, h->bm, h->bv, h->wswT, h->rawsc};
   for (float* q : p)
     if (q) (void)hipFree(q);
   delete h;
@@ -498,3 +519,5 @@ int mst_tcn_film_forward(const mst_tcn_film* f, const float* emb, int B, float* 
 }
 
 }  // extern "C"
+
+#include "tcn_train.inc"

@@ -2,12 +2,17 @@
 `src/tcn_mixer.py`, driven by `inference/inference_e2e_style_transfer.py:124-177`).
 
 Same class names, constructor arguments, defaults and `state_dict` keys as the reference, so a reference checkpoint's
-`tcn_state_dict` / `film_generator_state_dict` loads with `strict=True`.  Two backends:
+`tcn_state_dict` / `film_generator_state_dict` loads with `strict=True`.  Backends:
 
   * `backend = "hip"` (default): inference on the kernels of `csrc/tcn.hip` (exact fp32 MFMA).  Needs `eval()`, CUDA
     tensors, fp32 and no gradients; anything else RAISES and names the opt-in (no silent library path, no CPU fallback).
   * `backend = "torch"`: the plain module tree on PyTorch (any device, any dtype, autograd).  It is the opt-in for
     training and the arithmetic the tests pin to the reference.
+  * `backend = "hip-train"` (TCNMixer only): training on the kernels of `csrc/tcn_train.inc`.  In `train()` mode the
+    forward uses batch statistics and updates the running ones, and with grad enabled it is an autograd function whose
+    backward returns the gradients of x, of the FiLM tensors and of every parameter.  In `eval()` without gradients it
+    is the inference path of "hip".  The device weights follow in-place parameter updates (an optimiser step) through a
+    device kernel, without a host copy.  CUDA fp32 only; `eval()` with gradients raises and names `backend = "torch"`.
 """
 import ctypes as C
 import math
@@ -20,6 +25,7 @@ from . import _lib
 
 STEM_ORDER = ("vocals", "bass", "drums", "other")
 _BACKENDS = ("hip", "torch")
+_MIXER_BACKENDS = _BACKENDS + ("hip-train",)
 
 
 class CausalConv1d(nn.Module):
@@ -108,6 +114,11 @@ def _hip_refusal(module, what, *tensors):
     if torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in tensors)
                                     or any(p.requires_grad for p in module.parameters())):
         return f"{what}: the HIP backend has no backward; call under torch.no_grad()"
+    return _tensor_refusal(what, *tensors)
+
+
+def _tensor_refusal(what, *tensors):
+    """The device / dtype part of _hip_refusal."""
     for t in tensors:
         if t is None:
             continue
@@ -278,10 +289,10 @@ class TCNMixer(nn.Module):
             self._hip = _Handle(ptr, _lib.lib().mst_tcn_destroy, key, device)
         return self._hip
 
-    def _forward_hip(self, x, film, tap_blocks=()):
+    def _forward_hip(self, x, film, tap_blocks=(), handle=None):
         """x (B, 8, T) cuda fp32, film (B, nb, 4, H) or None -> y, [hidden state after each block of tap_blocks]."""
         dev = x.device
-        h = self._handle(dev)
+        h = handle or self._handle(dev)
         x = x.contiguous()
         B, _, T = x.shape
         H = self.hidden_channels
@@ -312,17 +323,143 @@ class TCNMixer(nn.Module):
                                              _lib.dptr(ws), nbytes, _lib.stream_ptr(dev)), "mst_tcn_forward")
         return y, taps_out
 
+    # ---- HIP, training ---------------------------------------------------------------------------------------------
+    def _norms(self):
+        return [getattr(b, f"norm{l}") for b in self.blocks for l in (1, 2)]
+
+    def _train_params(self):
+        """Every parameter in the order _TCNTrainFn.backward returns gradients."""
+        ps = [self.input_conv.weight, self.input_conv.bias]
+        for b in self.blocks:
+            ps += [b.conv1.conv.weight, b.conv1.conv.bias, b.conv2.conv.weight, b.conv2.conv.bias,
+                   b.norm1.weight, b.norm1.bias, b.norm2.weight, b.norm2.bias]
+        return ps + [self.output_conv.weight, self.output_conv.bias]
+
+    def _handle_train(self, device, running_stats=False):
+        """The handle with its device weights current: built once from host copies, then refreshed on the device when a
+        parameter's version moved (mst_tcn_update_params: no host copy, no synchronisation).  The running statistics, which
+        every train-mode forward moves and only the inference path reads, are refreshed only with `running_stats`."""
+        state = self.state_dict(keep_vars=True)
+        msg = _tensor_refusal("TCNMixer (backend='hip-train')", *[v for v in state.values() if v.is_floating_point()])
+        if msg:
+            _raise_refusal(msg)
+        key = ("hip-train",) + tuple((k, v.data_ptr(), v.device, v.dtype) for k, v in state.items())
+        if self._hip is None or self._hip.key != key or self._hip.device != device:
+            self._hip = None
+            h = self._handle(device)
+            h.key, h.param_versions, h.stat_versions = key, None, None
+        h = self._hip
+        norms = self._norms()
+        params = self._train_params()
+        pv = tuple(p._version for p in params)
+        sv = tuple(b._version for n in norms for b in (n.running_mean, n.running_var)) if running_stats else h.stat_versions
+        if h.param_versions == pv and h.stat_versions == sv:
+            return h
+        w = _lib.TcnWeights()
+        keep = []
+
+        def put(field, t):
+            t = t.detach().contiguous()
+            keep.append(t)
+            setattr(w, field, t.data_ptr())
+
+        cat = lambda f: torch.stack([f(b, l) for b in self.blocks for l in (1, 2)])  # noqa: E731
+        if h.param_versions != pv:
+            put("input_w", self.input_conv.weight), put("input_b", self.input_conv.bias)
+            put("conv_w", cat(lambda b, l: getattr(b, f"conv{l}").conv.weight.detach()))
+            put("conv_b", cat(lambda b, l: getattr(b, f"conv{l}").conv.bias.detach()))
+            put("bn_w", cat(lambda b, l: getattr(b, f"norm{l}").weight.detach()))
+            put("bn_b", cat(lambda b, l: getattr(b, f"norm{l}").bias.detach()))
+            put("output_w", self.output_conv.weight), put("output_b", self.output_conv.bias)
+        if h.stat_versions != sv:
+            put("bn_mean", torch.stack([n.running_mean for n in norms])), put("bn_var", torch.stack([n.running_var for n in norms]))
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().mst_tcn_update_params(h.ptr, C.byref(w), _lib.stream_ptr(device)), "mst_tcn_update_params")
+        h.param_versions, h.stat_versions = pv, sv
+        return h
+
+    def _train_forward(self, x, film, want_save):
+        """Train-mode forward of the whole batch in one call (batch statistics).  Returns y, save (or None), handle;
+        `_last_batch_stats` keeps the batch mean and biased variance, (nb, 2, H) each."""
+        dev = x.device
+        h = self._handle_train(dev)
+        B, _, T = x.shape
+        if B * T < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+        nb, H = self.num_blocks, self.hidden_channels
+        y = torch.empty_like(x)
+        mean = torch.empty(nb * 2, H, device=dev, dtype=torch.float32)
+        var = torch.empty_like(mean)
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            nws = L.mst_tcn_train_workspace_bytes(h.ptr, B, T)
+            nsave = L.mst_tcn_train_save_bytes(h.ptr, B, T) if want_save else 0
+            if nws == 0 or (want_save and nsave == 0):
+                _lib.check(-1, "mst_tcn_train_workspace_bytes")
+            ws = torch.empty(nws, device=dev, dtype=torch.uint8)
+            save = torch.empty(nsave, device=dev, dtype=torch.uint8) if want_save else None
+            _lib.check(L.mst_tcn_forward_train(h.ptr, _lib.dptr(x), _lib.dptr(film), B, T, _lib.dptr(y), _lib.dptr(mean), _lib.dptr(var),
+                                               _lib.dptr(save), nsave, _lib.dptr(ws), nws, _lib.stream_ptr(dev)), "mst_tcn_forward_train")
+        # running statistics as nn.BatchNorm1d keeps them: (1 - m) * running + m * batch, unbiased variance
+        with torch.no_grad():
+            norms = self._norms()
+            unbiased = var * (B * T / (B * T - 1))
+            for m in sorted({float(n.momentum) for n in norms}):
+                idx = [i for i, n in enumerate(norms) if float(n.momentum) == m]
+                for bufs, stat in (([norms[i].running_mean for i in idx], mean), ([norms[i].running_var for i in idx], unbiased)):
+                    torch._foreach_mul_(bufs, 1.0 - m)
+                    torch._foreach_add_(bufs, [stat[i] for i in idx], alpha=m)
+            torch._foreach_add_([n.num_batches_tracked for n in norms], 1)
+        self._last_batch_stats = (mean.view(nb, 2, H), var.view(nb, 2, H))   # read by the tests
+        return y, save, h
+
+    def _forward_hip_train(self, x, film_params, fl):
+        what = "TCNMixer.forward (backend='hip-train')"
+        if self.training:
+            for n in self._norms():
+                if n.momentum is None:
+                    raise ValueError(f"{what}: BatchNorm1d momentum=None (cumulative average) is not supported; "
+                                     f"backend='torch' runs it")
+                if not n.track_running_stats or n.running_mean is None:
+                    raise ValueError(f"{what}: BatchNorm1d track_running_stats=False is not supported; backend='torch' runs it")
+        msg = _tensor_refusal(what, x, *fl)
+        if msg:
+            _raise_refusal(msg)
+        if x.dim() != 3 or x.shape[1] != self.in_channels:
+            raise ValueError(f"expected (B, {self.in_channels}, T) stems, got {tuple(x.shape)}")
+        B, nb, H = x.shape[0], self.num_blocks, self.hidden_channels
+        grad = torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in fl)
+                                            or any(p.requires_grad for p in self.parameters()))
+        if not self.training:
+            if grad:
+                _raise_refusal(f"{what}: gradients in eval() mode (frozen BatchNorm statistics) are not built")
+            film = _packed_film(film_params, B, nb, H) if self.use_film else None
+            return self._forward_hip(x, film, handle=self._handle_train(x.device, running_stats=True))[0]
+        if x.numel() == 0:
+            raise ValueError(f"{what}: empty input {tuple(x.shape)}")
+        film = None
+        if self.use_film:   # stacked with ops autograd follows (not the as_strided view of _packed_film)
+            film = torch.stack([torch.stack([film_params[i][k] for k in _FILM_KEYS], 1) for i in range(nb)], 1)
+            if tuple(film.shape) != (B, nb, 4, H):
+                raise ValueError(f"expected FiLM tensors of shape ({B}, {H}), got a stack of {tuple(film.shape)}")
+            film = film.contiguous()
+        if not grad:
+            return self._train_forward(x.contiguous(), film, want_save=False)[0]
+        return _TCNTrainFn.apply(self, x, film, *self._train_params())
+
     def forward(self, x, film_params=None):
         if self.use_film:
             if film_params is None:
                 raise ValueError("film_params must be provided when use_film=True")
             if len(film_params) != self.num_blocks:
                 raise ValueError(f"Expected {self.num_blocks} FiLM parameter dicts, got {len(film_params)}")
-        if self.backend not in _BACKENDS:
-            raise ValueError("backend must be 'hip' (default) or 'torch'")
+        if self.backend not in _MIXER_BACKENDS:
+            raise ValueError("backend must be 'hip' (default), 'torch' or 'hip-train'")
         if self.backend == "torch":
             return self._forward_torch(x, film_params)
         fl = [p[k] for p in film_params for k in _FILM_KEYS] if self.use_film else []
+        if self.backend == "hip-train":
+            return self._forward_hip_train(x, film_params, fl)
         msg = _hip_refusal(self, "TCNMixer.forward", x, *fl)
         if msg:
             _raise_refusal(msg)
@@ -335,6 +472,46 @@ class TCNMixer(nn.Module):
         stacked = torch.cat([stems_dict[s] for s in STEM_ORDER], dim=0).unsqueeze(0)
         out = self.forward(stacked, film_params=film_params).squeeze(0)
         return {s: out[2 * i:2 * i + 2, :] for i, s in enumerate(STEM_ORDER)}
+
+
+class _TCNTrainFn(torch.autograd.Function):
+    """TCNMixer in train() mode on the HIP kernels: y = f(x, film, parameters), gradients of all of them."""
+
+    @staticmethod
+    def forward(ctx, mixer, x, film, *params):
+        x = x.contiguous()
+        y, save, h = mixer._train_forward(x, film, want_save=True)
+        ctx.mixer, ctx.handle = mixer, h
+        # the parameters are saved for autograd's version check: the backward reads the handle's copies of them
+        ctx.save_for_backward(x, film, save, *params)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, film, save = ctx.saved_tensors[:3]
+        mixer, h = ctx.mixer, ctx.handle
+        dev = x.device
+        B, _, T = x.shape
+        nb, H, K = mixer.num_blocks, mixer.hidden_channels, mixer.kernel_size
+        dy = dy.contiguous()
+        new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)  # noqa: E731
+        g = dict(input_w=new(H, 8, 1), input_b=new(H), conv_w=new(nb, 2, H, H, K), conv_b=new(nb, 2, H), bn_w=new(nb, 2, H),
+                 bn_b=new(nb, 2, H), output_w=new(8, H, 1), output_b=new(8))
+        grads = _lib.TcnGrads(**{k: v.data_ptr() for k, v in g.items()})
+        dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        dfilm = torch.empty_like(film) if film is not None and ctx.needs_input_grad[2] else None
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            nws = L.mst_tcn_train_workspace_bytes(h.ptr, B, T)
+            ws = torch.empty(nws, device=dev, dtype=torch.uint8)
+            _lib.check(L.mst_tcn_backward(h.ptr, _lib.dptr(dy), _lib.dptr(x), _lib.dptr(film), B, T, _lib.dptr(save), save.numel(),
+                                          C.byref(grads), _lib.dptr(dx), _lib.dptr(dfilm), _lib.dptr(ws), nws, _lib.stream_ptr(dev)),
+                       "mst_tcn_backward")
+        out = [g["input_w"], g["input_b"]]
+        for i in range(nb):
+            out += [g["conv_w"][i, 0], g["conv_b"][i, 0], g["conv_w"][i, 1], g["conv_b"][i, 1],
+                    g["bn_w"][i, 0], g["bn_b"][i, 0], g["bn_w"][i, 1], g["bn_b"][i, 1]]
+        return (None, dx, dfilm, *out, g["output_w"], g["output_b"])
 
 
 def create_tcn_mixer(receptive_field_seconds=5.2, sample_rate=44100, use_film=False, hidden_channels=8, kernel_size=15,
