@@ -368,7 +368,9 @@ typedef struct mst_aug_clip {
 
 size_t mst_aug_workspace_bytes(int B, int T, int ir_len);
 /* stems_inout: dev [B][8][T] modified in place; decisions: host [B];
- * reverb_ir:   dev [B][ir_len] (rows of clips with reverb==0 are ignored; may be NULL if none) */
+ * reverb_ir:   dev [B][ir_len] (rows of clips with reverb==0 are ignored; may be NULL if none).
+ * Any T >= 1 and any ir_len >= 1 (shorter or longer than T): no limit on the number of 16 384-sample segments of a clip;
+ * the index arithmetic holds for T <= 2^24.                                                                          */
 int mst_aug_apply(const mst_aug_clip* decisions, int B, int T, float* stems_inout,
                   const float* reverb_ir, int ir_len, void* workspace, size_t workspace_bytes,
                   void* stream);

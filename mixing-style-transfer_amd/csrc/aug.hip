@@ -5,7 +5,9 @@
 //
 //   aug_chain_kernel   x*gain -> biquad (tilt) -> compressor -> 1-2 biquads (low-pass): one workgroup per (channel, segment) of
 //                      16 384 samples resident in LDS, float64 block-parallel IIR inside a segment, decoupled look-back between a
-//                      stream's segments (see the kernel's comment);
+//                      stream's segments (see the kernel's comment); any clip length: the look-back folds the earlier segments'
+//                      aggregates in tiles of what its LDS buffer holds (128 segments of a 4th-order filter, 256 of a biquad;
+//                      tested from T = 1 to 257 segments + 33 samples, index arithmetic checked for T <= 2^24);
 //                      one read and one write of every channel that has a decision.  scipy.signal.sosfilt is a sequential
 //                      fp64 DF2T recurrence; rounded to fp32 exactly where the reference calls `.float()`.
 //   aug_energy_kernel  per-stem mean square for the reverb redistribution weights (:410-416).
@@ -198,7 +200,7 @@ __device__ __forceinline__ void chain_post(unsigned long long* word, double v) {
 // aggregate Z (its final state from a zero start: needs nothing from other segments) and publishes it (`mine`); then the
 // workgroup reads the aggregates of ALL earlier segments of the stream (`first`, records `stride` words apart) -- in parallel,
 // one word per thread, polling the few that are not there yet -- and thread 0 folds them, s <- M^kFT s + Z_j for j = 0 .. nprev - 1,
-// into the state at this segment's start.  No segment waits for another one's RESULT, only for its aggregate, and all
+// into the state at this segment's start (through `zin`, in tiles of kFT / D segments: any number of segments).  No segment waits for another one's RESULT, only for its aggregate, and all
 // aggregates of a stream are produced at about the same time: the serial hand-over chain of the first version (14 hops per
 // stream and filter) is one hop deep.
 template <int D>
@@ -236,21 +238,33 @@ __device__ __forceinline__ void chain_scan(double (&z)[D], const double (*Mp)[16
 #pragma unroll
     for (int i = 0; i < D; ++i) chain_post(mine + i, Z[i]);
   }
-  for (int i = tid; i < nprev * D; i += kFT) zin[i] = chain_wait(first + (size_t)(i / D) * stride + (i % D), err);
-  __syncthreads();
-  if (tid == 0) {
-    double s[D], t[D];
+  // zin holds kFT words = kFT / D segments: a longer stream is folded tile by tile (thread 0 keeps s in registers between the
+  // tiles; the second barrier of a tile also frees zin for the next gather).  One tile -- every stream of up to kFT / D + 1
+  // segments -- is two barriers, and the fold order is j = 0 .. nprev - 1 whatever the tiling.
+  constexpr int kTile = kFT / D;
+  double s[D];
 #pragma unroll
-    for (int i = 0; i < D; ++i) s[i] = 0.0;
-    for (int j = 0; j < nprev; ++j) {
-      matvec<D>(Mp[kFPow - 1], s, t);
+  for (int i = 0; i < D; ++i) s[i] = 0.0;
+  for (int j0 = 0;;) {   // nprev is block-uniform: every thread takes the same barriers
+    const int nt = min(nprev - j0, kTile);
+    for (int i = tid; i < nt * D; i += kFT) zin[i] = chain_wait(first + (size_t)(j0 + i / D) * stride + (i % D), err);
+    __syncthreads();
+    const bool last = j0 + nt >= nprev;
+    if (tid == 0) {
+      double t[D];
+      for (int j = 0; j < nt; ++j) {
+        matvec<D>(Mp[kFPow - 1], s, t);
 #pragma unroll
-      for (int i = 0; i < D; ++i) s[i] = t[i] + zin[j * D + i];
+        for (int i = 0; i < D; ++i) s[i] = t[i] + zin[j * D + i];
+      }
+      if (last)
+#pragma unroll
+        for (int i = 0; i < D; ++i) seg[i] = s[i];
     }
-#pragma unroll
-    for (int i = 0; i < D; ++i) seg[i] = s[i];
+    __syncthreads();
+    if (last) break;
+    j0 += nt;
   }
-  __syncthreads();
   double C[D];   // state at the start of this wave's first chunk: C_0 = seg, C_(w+1) = M^64 C_w + W_w
 #pragma unroll
   for (int i = 0; i < D; ++i) C[i] = seg[i];
@@ -542,6 +556,12 @@ __device__ __forceinline__ v2f cmac(v2f acc, v2f a, v2f w) {
   asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(d) : "v"(a), "v"(w), "v"(t));                                    // (a.x w.x, a.x w.y) + t
   return d;
 }
+// rev = 0.7 * mix + 0.3 * y and stem + (rev * w) * 0.3 with the roundings written out (one rounded product, one fused multiply-add):
+// the 16-byte path and the per-sample path of rev_mac_ifft_kernel must give the same bits -- left to the compiler's contraction,
+// the per-sample path fused mix * 0.7 in the right channel where the 16-byte path fuses y * 0.3, and an aligned and a misaligned
+// clip (or an interior and an edge block of one clip) differed in the last bit.
+__device__ __forceinline__ float wet_mix(float mix, float y) { return __builtin_fmaf(y, 0.3f, mix * 0.7f); }
+__device__ __forceinline__ float wet_add(float x, float rev, float w) { return __builtin_fmaf(rev * w, 0.3f, x); }
 struct RevLds {
   float2 tw[FftPlan<kNfft>::TW];
   union {
@@ -673,15 +693,15 @@ __global__ __launch_bounds__(kRevWaves * 64) void rev_mac_ifft_kernel(const RevP
         const float* f = reinterpret_cast<const float*>(x);
         const float mL = ((f[0 * 4 + e] + f[2 * 4 + e]) + f[4 * 4 + e]) + f[6 * 4 + e];   // ((v+b)+d)+o
         const float mR = ((f[1 * 4 + e] + f[3 * 4 + e]) + f[5 * 4 + e]) + f[7 * 4 + e];
-        revL[e] = mL * 0.7f + y.x * 0.3f, revR[e] = mR * 0.7f + y.y * 0.3f;
+        revL[e] = wet_mix(mL, y.x), revR[e] = wet_mix(mR, y.y);
       }
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         const float* r = (c & 1) ? revR : revL;
         const float w = pr[c >> 1];
         float4 o4;
-        o4.x = x[c].x + (r[0] * w) * 0.3f, o4.y = x[c].y + (r[1] * w) * 0.3f;
-        o4.z = x[c].z + (r[2] * w) * 0.3f, o4.w = x[c].w + (r[3] * w) * 0.3f;
+        o4.x = wet_add(x[c].x, r[0], w), o4.y = wet_add(x[c].y, r[1], w);
+        o4.z = wet_add(x[c].z, r[2], w), o4.w = wet_add(x[c].w, r[3], w);
         *reinterpret_cast<float4*>(p.stems + co + (size_t)c * p.T + n) = o4;
       }
     }
@@ -694,8 +714,8 @@ __global__ __launch_bounds__(kRevWaves * 64) void rev_mac_ifft_kernel(const RevP
     if (n < 0 || n >= p.T) continue;
     const float2 z = v[out_reg<kNfft>(q)];
     const float yL = z.x * scale, yR = -z.y * scale;
-    const float revL = mix_at(p.stems, co, p.T, 0, n, mode) * 0.7f + yL * 0.3f;  // audio*(1-0.3) + reverb*0.3
-    const float revR = mix_at(p.stems, co, p.T, 1, n, mode) * 0.7f + yR * 0.3f;
+    const float revL = wet_mix(mix_at(p.stems, co, p.T, 0, n, mode), yL);  // audio*(1-0.3) + reverb*0.3
+    const float revR = wet_mix(mix_at(p.stems, co, p.T, 1, n, mode), yR);
     if (mode == 2) {
       p.stems[co + n] = revL;
       p.stems[co + (size_t)p.T + n] = revR;
@@ -703,8 +723,8 @@ __global__ __launch_bounds__(kRevWaves * 64) void rev_mac_ifft_kernel(const RevP
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         float* xs = p.stems + co + (size_t)(2 * s) * p.T;
-        xs[n] = xs[n] + (revL * pr[s]) * 0.3f;
-        xs[(size_t)p.T + n] = xs[(size_t)p.T + n] + (revR * pr[s]) * 0.3f;
+        xs[n] = wet_add(xs[n], revL, pr[s]);
+        xs[(size_t)p.T + n] = wet_add(xs[(size_t)p.T + n], revR, pr[s]);
       }
     }
   }

@@ -303,6 +303,8 @@ class AudioAugmenter:
     seeded run makes bit-identical decisions; the audio is then processed by libmst.so (`mst_aug_apply`).
     `augment_stems` accepts the reference's {stem: (2, T)} dict or a batched {stem: (B, 2, T)} dict (clips are drawn
     one after the other, as consecutive reference calls would).  `last_trace` keeps the decisions of the last call.
+    Clips may have any length: a stream is cut into 16 384-sample segments whose filter states are handed on exactly, however
+    many there are (tested from 1 sample to 4.2 M, tests/test_aug_edges_gpu.py).
     """
 
     def __init__(self, sample_rate=44100, gain_range=9.0, prob=0.5):

@@ -36,6 +36,24 @@ def make_ir(sr: int, decay=0.5) -> torch.Tensor:
     return torch.exp(-t / (decay / 4)) * torch.randn(L) * 0.1
 
 
+def tilt_sos(high: bool, sr=44100):
+    """mixing_utils.py:421-433: the two fixed tilt filters."""
+    return butter(2, 2000, btype="high", fs=sr, output="sos") if high else \
+        butter(2, 500, btype="low", fs=sr, output="sos")
+
+
+def lowpass(x: torch.Tensor, fc: float, sr=44100, order=4) -> torch.Tensor:
+    """mixing_utils.py:449-456 (the reference uses order 4)."""
+    return _sosfilt32(butter(order, fc, btype="low", fs=sr, output="sos"), x)
+
+
+def reverb_redistribute(out: dict, ir: torch.Tensor) -> dict:
+    """mixing_utils.py:403-416: reverb on the mix, handed back to the stems in proportion to their energies."""
+    mix = reverb(sum(out.values()), ir)
+    tot = sum([torch.mean(s ** 2) for s in out.values()]) + 1e-8
+    return {name: s + mix * (torch.mean(s ** 2) / tot) * 0.3 for name, s in out.items()}
+
+
 def augment_stems(stems_dict, sr=44100, gain_range=9.0, prob=0.5):
     """stems_dict {stem: (2,T)} -> (aug dict, trace dict)."""
     out, trace = {}, {}
@@ -49,23 +67,17 @@ def augment_stems(stems_dict, sr=44100, gain_range=9.0, prob=0.5):
         if torch.rand(1) < prob:
             hi = bool(torch.rand(1) < 0.5)
             t["tilt"] = "high" if hi else "low"
-            sos = butter(2, 2000, btype="high", fs=sr, output="sos") if hi else \
-                butter(2, 500, btype="low", fs=sr, output="sos")
-            x = _sosfilt32(sos, x)
+            x = _sosfilt32(tilt_sos(hi, sr), x)
         if torch.rand(1) < prob:
             t["comp"] = True
             x = compress(x)
         if torch.rand(1) < prob:
             fc = torch.rand(1) * 8000 + 4000
             t["cutoff"] = fc.item()
-            x = _sosfilt32(butter(4, fc.item(), btype="low", fs=sr, output="sos"), x)
+            x = lowpass(x, fc.item(), sr)
         out[name], trace[name] = x, t
     if torch.rand(1) < prob:
-        mix = sum(out.values())
         ir = make_ir(sr)
         trace["reverb_ir"] = ir
-        mix = reverb(mix, ir)
-        tot = sum([torch.mean(s ** 2) for s in out.values()]) + 1e-8
-        for name in out:
-            out[name] = out[name] + mix * (torch.mean(out[name] ** 2) / tot) * 0.3
+        out = reverb_redistribute(out, ir)
     return out, trace
