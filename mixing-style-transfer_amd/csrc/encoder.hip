@@ -257,6 +257,9 @@ struct ConvParams {
   // elements of the layout's 16-byte units' scalar type (floats: frames * cm_mels * 8)
   const void* in_lo;
   int cm_mels, cm_overlap;
+  // conv2_rows_kernel: top / bottom tile pairs per plane, fold tiles per plane (0 or 1), and the sets of a band that hold
+  // pairs (4 per set; the fold tiles, 8 per set, follow them: sets_per_band counts both)
+  int rt_blocks, rt_fold, rt_pair_sets;
 };
 
 typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
@@ -726,6 +729,249 @@ __global__ __launch_bounds__(kConvThreads) void conv_kernel(const ConvParams p) 
   }
 #endif
   if ((MODE == 1 || MODE == 3) && st_band >= 0) flush_stats<NT, C::COUT>(st, p.stats, st_band, lane);
+}
+
+// ------------------------------------------------------------------------------------------
+// conv2, eval forward, 10-row input plane (H1 == 10, FD == 2: output rows 0 .. 7 reach the pool): ROW-PURE 4 x 16 tiles.
+// conv_kernel<2, 2, 0> with another tiling -- same chunks, taps, weight fragments, loads and per-element summation order
+// (chunk -> tap -> 4 channels), so the results are the same bits.  An M-tile is ONE output row x 16 columns, so every
+// (output row, tap row) pair that reads nothing but zero padding is a whole M-tile and its MFMAs are left out:
+//   top tile (rows 0 .. 3):    tap row 0 skips M-tiles 0, 1, 2; tap row 1 skips 0, 1; tap row 2 skips 0      22 of 28 units
+//   bottom tile (rows 4 .. 7): tap row 6 skips M-tile 3 (input row 10 of a 10-row plane)                      27 of 28 units
+// (the two-row M-tiles of conv_kernel's TS layout can leave out 4 of these 7 pairs only).  In the MFMA's D layout lane
+// (j, g) holds rows r0 .. r0 + 3 x columns 4 g .. 4 g + 3 of channel j: one whole pooling window, no cross-lane max.
+// A plane is two tile rows x out_cols / 4 column blocks.  Waves w and w + 4 share a SIMD and take the top and the bottom
+// tile of one block: every SIMD carries 22 + 27 units up to the chunk's barrier.  The last out_cols % 4 windows:
+//   1 or 2: one FOLD tile per plane, both tile rows x 2 windows, M-tile t = (row t | row t + 4) x 8 columns (nothing to skip);
+//   3:      one more top / bottom pair, partly outside the plane.
+// Fold tiles fill sets of their own behind a band's pair sets (a set ends every chunk at one barrier: kinds of unequal work
+// do not mix).  All kinds share the patch's column pitch, so the tap offsets are one code; only a per-lane base differs.
+// ------------------------------------------------------------------------------------------
+struct RowTiles {
+  static constexpr int PC = 22;         // patch columns of a pair tile (16 + halo) = the common row pitch
+  static constexpr int PR = 10;         // patch rows of a pair tile (4 + halo)
+  static constexpr int FR = 14, FC = 14;   // patch rows, columns of a fold tile (8 + halo)
+  // channel pitch: >= the fold tile's last element + 1 (13 * 22 + 14 = 300) and == 16 (mod 32) -- ds_read_b32 banks per
+  // 32-lane half, i.e. per pair of k-groups: 16 consecutive floats (pair tile) or two runs of 8, 88 floats apart (fold
+  // tile) of k-group 0 and the same + 16 of k-group 1 fall into disjoint banks
+  static constexpr int CP = 304;
+  static constexpr int PATCH = 4 * CP;
+};
+
+__global__ __launch_bounds__(kConvThreads) void conv2_rows_kernel(const ConvParams p) {
+  using C = CC<2, 2>;
+  using GEO = ConvGeom<2, 2>;
+  using R = RowTiles;
+  constexpr int MT = 4, NT = C::NT, NCH = C::NCH, PC = R::PC, CP = R::CP;
+  constexpr int WBP = GEO::WBP, NWF = GEO::NWF;
+  constexpr int NPFK = 16;                                        // patch pieces: 4 channels x 4 runs of 64 elements
+  constexpr int NPIECE = NPFK + NWF, PPT = (NPIECE + 48) / 49;    // prefetch pieces, pieces issued per tap
+  static_assert(MT == C::MT && (R::PR - 1) * PC + PC <= 256 && R::FR * 16 <= 256, "4 pieces of 64 lanes cover a channel of either kind");
+  static_assert((R::FR - 1) * PC + R::FC <= CP && CP % 32 == 16, "channel pitch, see RowTiles");
+  static_assert((size_t)(2 * WBP + kConvWaves * R::PATCH) * sizeof(float) <= 160 * 1024, "conv2_rows_kernel must fit one CU's LDS");
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  float* wbuf = smem;                                   // [2][WBP]
+  float* pbuf = smem + 2 * WBP + wave * R::PATCH;       // wave-private patch [4][CP], rows at pitch PC
+
+  const int G = gridDim.x;
+  const int wg = mst::xcd_remap(blockIdx.x, G);
+  const int total_sets = p.nsub * p.sets_per_band;
+  const int my_sets = wg < total_sets ? (total_sets - wg + G - 1) / G : 0;   // round-robin, as conv_kernel
+  const int nq = my_sets * NCH;
+  const int fold_blk = p.out_cols >> 2;                 // column block of the fold tile
+
+  struct RTile {
+    int valid, clip, band, blk, kind;                   // kind 0 / 1: top / bottom tile of column block blk, 2: fold tile
+  };
+  auto decode = [&](int q) __attribute__((always_inline)) {
+    const int s = wg + (q / NCH) * G;
+    RTile t;
+    t.band = min(s / p.sets_per_band, p.nsub - 1);
+    const int sb = s - t.band * p.sets_per_band;
+    const bool fold = sb >= p.rt_pair_sets;
+    const int idx = fold ? (sb - p.rt_pair_sets) * kConvWaves + wave : sb * 4 + (wave & 3);
+    const int per = fold ? p.rt_fold : p.rt_blocks;     // tiles (fold) or top / bottom pairs per plane
+    t.valid = q < nq && idx < p.B * per;
+    t.clip = t.valid ? idx / per : 0;
+    t.blk = fold ? fold_blk : (t.valid ? idx - t.clip * per : 0);
+    t.kind = fold ? 2 : wave >> 2;
+    return t;
+  };
+
+  // A-fragment base (floats, inside the wave patch): row i = lane & 15 of M-tile t sits at ap[t * PC (+ the tap offset) --
+  // pair tiles: row r0 + t, column i; fold tiles: row 4 (i >> 3) + t, column i & 7 (lane group g of the D layout then holds
+  // rows 4 (g >> 1) .. + 3 x columns 4 (g & 1) .. + 3: again one whole window)
+  const int kq = lane >> 4, ai = lane & 15;
+  const float* const ap_pair = pbuf + kq * CP + ai;
+  const float* const ap_fold = pbuf + kq * CP + 4 * (ai >> 3) * PC + (ai & 7);
+  const float* ap = ap_pair;
+
+  // ---- prefetch state of the NEXT chunk (raw buffer loads: a lane outside the plane gets an offset beyond the buffer and
+  // reads zeros; lane offsets once per tile, one scalar offset per piece)
+  f32x4 wreg[NWF];
+  float pf[NPFK];
+  __amdgpu_buffer_rsrc_t nrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, 0, 0x00020000);
+  __amdgpu_buffer_rsrc_t nwrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wfrag), 0, 0, 0x00020000);
+  unsigned nvoff[4] = {0x80000000u, 0x80000000u, 0x80000000u, 0x80000000u}, nsoff = 0;   // per run: lane offset (bytes); scalar offset
+  int nsaddr[4] = {-1, -1, -1, -1};   // per run: where this lane's element goes in a channel of the patch, -1: nowhere
+
+  auto prefetch_setup = [&](int q, const RTile& t) __attribute__((always_inline)) {
+    const int chunk = q % NCH;
+    const float* src = p.in + (size_t)t.clip * p.in_clipstride + (size_t)t.band * p.in_bandoff + (size_t)(4 * chunk) * p.in_cstride;
+    const float* wsrc = p.wfrag + ((size_t)t.band * NCH + chunk) * WBP;
+    nrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src), 0, (unsigned)(4 * p.in_cstride) * 4u, 0x00020000);
+    nwrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wsrc), 0, (unsigned)WBP * 4u, 0x00020000);
+    if (chunk == 0) {   // the lane offsets belong to the TILE
+      const bool fold = t.kind == 2;
+      const int row0 = (t.kind == 1 ? 4 : 0) - 3, col0 = 16 * t.blk - 3;
+      const int rbase = max(row0, 0), cbase = max(col0, 0);   // scalar part (>= 0: soffset is unsigned)
+      nsoff = (unsigned)(rbase * p.in_cols + cbase) * 4u;
+      int ln = lane;
+      asm volatile("" : "+v"(ln));   // recompute per tile: hoisted out of the chunk loop the 20 lane constants below spill
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {   // flat element e = lane + 64 j over 10 x 22 (pair) or 14 x 16 (fold, 14 columns used)
+        const int e = ln + 64 * j;
+        const int r = fold ? e >> 4 : e / PC, c = fold ? e & 15 : e % PC;
+        const bool in_patch = fold ? (r < R::FR && c < R::FC) : r < R::PR;
+        const int rin = row0 + r, cin = col0 + c;
+        const bool ok = t.valid && in_patch && rin >= 0 && rin < p.in_rows && cin >= 0 && cin < p.in_cols;
+        nvoff[j] = ok ? (unsigned)((rin - rbase) * p.in_cols + (cin - cbase)) * 4u : 0x80000000u;
+        nsaddr[j] = in_patch ? r * PC + c : -1;
+      }
+    }
+  };
+  auto prefetch_piece = [&](int i) __attribute__((always_inline)) {  // i is a compile-time constant after unrolling
+    if (i < NPFK) {
+      pf[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(nrsrc, nvoff[i & 3], nsoff + (unsigned)((i >> 2) * p.in_cstride) * 4u, 0));
+    } else if (i < NPIECE) {
+      wreg[i - NPFK] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(nwrsrc, (unsigned)tid * 16u, (unsigned)(kConvThreads * (i - NPFK)) * 16u, 0));
+    }
+  };
+
+  f32x4 acc[MT][NT];
+  RTile cur{}, nxt{};
+  nxt = decode(0);
+  if (nq > 0) {
+    prefetch_setup(0, nxt);
+#pragma unroll
+    for (int i = 0; i < NPIECE; ++i) prefetch_piece(i);
+  }
+#ifdef MST_TRACE
+  long long trc[5] = {0, 0, 0, 0, 0};   // cycles: staging, barrier wait, taps, -; chunks
+  const long long trc_start = clock64();
+#endif
+  for (int q = 0; q < nq; ++q) {
+    float* wb = wbuf + (q & 1) * WBP;
+#ifdef MST_TRACE
+    const long long tq0 = clock64();
+#endif
+    // stage the prefetched chunk into LDS (out-of-plane elements were loaded as zeros)
+#pragma unroll
+    for (int i = 0; i < NWF; ++i) reinterpret_cast<f32x4*>(wb)[tid + kConvThreads * i] = wreg[i];
+#pragma unroll
+    for (int i = 0; i < NPFK; ++i)
+      if (nsaddr[i & 3] >= 0) pbuf[(i >> 2) * CP + nsaddr[i & 3]] = pf[i];
+#ifdef MST_TRACE
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const long long tq1 = clock64();
+#endif
+    __syncthreads();
+#ifdef MST_TRACE
+    const long long tq2 = clock64();
+    trc[0] += tq1 - tq0, trc[1] += tq2 - tq1, trc[4] += 1;
+#endif
+    cur = nxt;
+    if ((q + 1) % NCH == 0) nxt = decode(q + 1);   // the tile changes every NCH chunks only
+    prefetch_setup(q + 1, nxt);   // past the end this re-reads valid memory and is never staged
+    const int chunk = q % NCH;
+    if (chunk == 0) {
+      ap = cur.kind == 2 ? ap_fold : ap_pair;
+#pragma unroll
+      for (int t = 0; t < MT; ++t)
+#pragma unroll
+        for (int n = 0; n < NT; ++n) acc[t][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    // 49 taps as in conv_kernel; a tap row whose M-tiles in MASK see only padding issues no MFMAs for them.  The branches are
+    // wave-uniform and sit BETWEEN tap rows; inside a tap the issue order is conv_kernel's
+    {
+      float a[2][MT], b[2][NT];
+#pragma unroll
+      for (int t = 0; t < MT; ++t) a[0][t] = ap[t * PC];
+#pragma unroll
+      for (int n = 0; n < NT; ++n) b[0][n] = wb[n * 64 + lane];
+      auto taps = [&](auto LO_, auto HI_, auto MASK_) __attribute__((always_inline)) {
+        constexpr int LO = decltype(LO_)::value, HI = decltype(HI_)::value, MASK = decltype(MASK_)::value;
+#pragma unroll
+        for (int tap = LO; tap < HI; ++tap) {
+          const int cu = tap & 1, nx = cu ^ 1;
+          const int off = ((tap + 1) / 7) * PC + ((tap + 1) % 7);
+#pragma unroll
+          for (int i = 0; i < MT * NT; ++i) {
+            const int t = i / NT, n = i % NT;
+            if (!((MASK >> t) & 1)) acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[cu][t], b[cu][n], acc[t][n], 0, 0, 0);
+            if (tap + 1 < 49) {
+              if (i < NT) b[nx][i] = wb[((tap + 1) * NT + i) * 64 + lane];   // B first: needed by the next tap's MFMA 0
+              else if (i < MT + NT) a[nx][i - NT] = ap[(i - NT) * PC + off];
+            }
+            if (i >= MT + NT && i - (MT + NT) < PPT) prefetch_piece(tap * PPT + (i - (MT + NT)));
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+      };
+      // ONE branch for the top tile's three short tap rows: the compiler alternates an accumulator between two registers from
+      // MFMA to MFMA, so where the arms of a branch differ by an odd number of MFMAs on it the shorter arm ends in a copy
+      // (v_mov_b64 inside the stream); rows 0 .. 2 together differ by 21, 14, 7 taps on M-tiles 0, 1, 2 -- two tiles to copy,
+      // where a branch per row copies 3 + 2 + 1
+      using std::integral_constant;
+      using I0 = integral_constant<int, 0>;
+      using I7 = integral_constant<int, 7>;
+      using I14 = integral_constant<int, 14>;
+      using I21 = integral_constant<int, 21>;
+      using I42 = integral_constant<int, 42>;
+      using I49 = integral_constant<int, 49>;
+      if (cur.kind == 0) {
+        taps(I0{}, I7{}, integral_constant<int, 0b0111>{});
+        taps(I7{}, I14{}, integral_constant<int, 0b0011>{});
+        taps(I14{}, I21{}, integral_constant<int, 0b0001>{});
+      } else {
+        taps(I0{}, I21{}, I0{});
+      }
+      taps(I21{}, I42{}, I0{});
+      if (cur.kind == 1) taps(I42{}, I49{}, integral_constant<int, 0b1000>{});
+      else taps(I42{}, I49{}, I0{});
+    }
+#ifdef MST_TRACE
+    trc[2] += clock64() - tq2;
+#endif
+    if (chunk == NCH - 1 && cur.valid) {
+      // epilogue: y = A*acc + C, ReLU, max over the lane's 16 accumulators of N-tile n = one 4 x 4 window
+      const int j = lane & 15, g = lane >> 4;
+      const float2* aff = p.aff + ((size_t)cur.clip * p.nsub + cur.band) * C::COUT;
+      const int pr = cur.kind == 2 ? g >> 1 : cur.kind;
+      const int pc = 4 * cur.blk + (cur.kind == 2 ? g & 1 : g);
+#pragma unroll
+      for (int n = 0; n < NT; ++n) {
+        const int ch = n * 16 + j;
+        const float2 ac = aff[ch];
+        float m = 0.f;  // ReLU floor
+#pragma unroll
+        for (int t = 0; t < MT; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) m = fmaxf(m, fmaf(acc[t][n][r], ac.x, ac.y));
+        if (pc < p.out_cols)  // pool_in[clip][(band*64 + ch)*2 + pr][pc]
+          p.out[(((size_t)cur.clip * p.nsub + cur.band) * C::COUT + ch) * p.out_rows * p.out_cols + (size_t)pr * p.out_cols + pc] = m;
+      }
+    }
+  }
+#ifdef MST_TRACE
+  if (lane == 0 && p.yraw) {
+    float* o = p.yraw + (blockIdx.x * kConvWaves + wave) * 8;
+    for (int i = 0; i < 5; ++i) o[i] = (float)trc[i];
+    o[5] = (float)(clock64() - trc_start);
+  }
+#endif
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3536,6 +3782,18 @@ hipError_t launch_conv(const ConvParams& cp, int grid, hipStream_t st) {
   return hipGetLastError();
 }
 
+hipError_t launch_conv2_rows(const ConvParams& cp, int grid, hipStream_t st) {
+  const size_t lds = (size_t)(2 * ConvGeom<2, 2>::WBP + kConvWaves * RowTiles::PATCH) * sizeof(float);
+  static unsigned long long attr_set = 0;   // per-device bit mask: the attribute belongs to the device
+  if (mst::first_use_on_device(attr_set)) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_rows_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(conv2_rows_kernel, dim3(grid), dim3(kConvThreads), lds, st, cp);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 extern "C" {
@@ -3982,7 +4240,21 @@ int mst_encoder_forward_in(const mst_encoder* e, const mst_logmel_in* lin, int f
       if (!trace_buf2) (void)hipMalloc(&trace_buf2, 256 * kConvWaves * 8 * sizeof(float));
       cp.yraw = trace_buf2;
 #endif
-      err = launch_conv<2, 2>(cp, g, st);
+      // 10-row planes (FD == 2: the 20-mel sub-bands): row-pure 4 x 16 tiles (conv2_rows_kernel); MST_CONV2_TILES=8x8, read
+      // per launch, keeps conv_kernel's 8 x 8 tiles there too (same bits: the yardstick of tests/test_conv2_row_tiles_gpu.py,
+      // and A/B timing).  H1 == 10 exactly: the kernel's bottom tile leaves out input row 10 as padding (an 11-row plane,
+      // split_size 35, has one)
+      const char* tiles_env = getenv("MST_CONV2_TILES");
+      if (e->FD == 2 && e->H1 == 10 && !(tiles_env && !strcmp(tiles_env, "8x8"))) {
+        const int rem = L.W2 % 4;
+        cp.rt_blocks = L.W2 / 4 + (rem == 3);
+        cp.rt_fold = rem == 1 || rem == 2;
+        cp.rt_pair_sets = (B * cp.rt_blocks + 3) / 4;
+        cp.sets_per_band = cp.rt_pair_sets + (B * cp.rt_fold + kConvWaves - 1) / kConvWaves;
+        err = launch_conv2_rows(cp, std::min(grid, ns * cp.sets_per_band), st);
+      } else {
+        err = launch_conv<2, 2>(cp, g, st);
+      }
 #ifdef MST_TRACE
       {
         static int calls = 0;
