@@ -13,10 +13,17 @@ embeddings for the two styles,
     cycle = tcn(out, film(target_emb, input_emb))
     loss  = MRSTFT(out, target) + lambda_cycle * MRSTFT(cycle, input)
 
-AdamW, and the reference's two clip_grad_norm_ calls.  The reference's style term -- the cosine distance between the
-frozen encoder's embedding of `out` and the target embedding -- is NOT part of this loop: the gradient of the encoder with
-respect to its input waveform does not exist on the HIP path yet, so the supervised MRSTFT term stands in for it.
-The same seed prints the same losses: every kernel of the step has a fixed summation order."""
+AdamW, and the reference's two clip_grad_norm_ calls.
+
+`--style-weight W` (default 0: the loop above, unchanged) adds the reference's style term (:192-224),
+
+    loss += W * cosine_distance_loss(encoder(out_stems, deferred_features), encoder(target_stems, deferred_features))
+
+through a FROZEN MixingStyleEncoder in eval mode (`--encoder-checkpoint`, else randomly initialised).  The gradient reaches
+the TCN through the encoder's input waveform: stage A (STFT -> mel -> log) forward and backward in HIP, the conv trunk on
+PyTorch-ROCm autograd (`encoder_backend="torch"`; the hand-written eval trunk has no input gradient yet).  The mixing
+features of `out` condition the encoder as constants, as in the reference ("no grad for feature extractor").
+With W = 0 the same seed prints the same losses: every kernel of the step has a fixed summation order."""
 import argparse
 import os
 import sys
@@ -24,7 +31,9 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mst_amd.loss import MultiResolutionSTFTLoss  # noqa: E402
+from mst_amd.loss import MultiResolutionSTFTLoss, cosine_distance_loss  # noqa: E402
+from mst_amd.mixing_utils import STEMS, deferred_features  # noqa: E402
+from mst_amd.model import MixingStyleEncoder  # noqa: E402
 from mst_amd.synth import synth_batch  # noqa: E402
 from mst_amd.tcn_mixer import TCNFiLMGenerator, TCNMixer  # noqa: E402
 
@@ -50,6 +59,10 @@ def main(argv=None):
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--lambda-cycle", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--style-weight", type=float, default=0.0,
+                    help="weight of the style term 1 - cos(encoder(out), encoder(target)) through the frozen encoder (0 = off)")
+    ap.add_argument("--encoder-checkpoint", default=None,
+                    help="MixingStyleEncoder checkpoint (a state_dict, or a dict holding 'model_state_dict'); default: random weights")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("train_tcn_mixer.py needs a GPU (backend='hip-train' has no CPU fallback)")
@@ -67,17 +80,35 @@ def main(argv=None):
     emb_in = torch.nn.functional.normalize(torch.randn(a.batch_size, a.embed_dim, generator=g), dim=1).to(dev)
     emb_tg = torch.nn.functional.normalize(torch.randn(a.batch_size, a.embed_dim, generator=g), dim=1).to(dev)
 
+    encoder = style_target = None
+    if a.style_weight > 0:   # (after everything above: the W = 0 loop draws the same random numbers as before)
+        as_stems = lambda t: {s: t[:, 2 * i:2 * i + 2] for i, s in enumerate(STEMS)}
+        feats = deferred_features(64).expand(a.batch_size, 64).to(dev)   # filled on the device from the encoder's own stage-A launch
+        encoder = MixingStyleEncoder(embed_dim=a.embed_dim, feature_dim=64, encoder_backend="torch")
+        if a.encoder_checkpoint:
+            sd = torch.load(a.encoder_checkpoint, map_location="cpu")
+            encoder.load_state_dict(sd.get("model_state_dict", sd))
+        encoder = encoder.to(dev).eval()
+        for q in encoder.parameters():
+            q.requires_grad_(False)
+        with torch.no_grad():
+            style_target = encoder(as_stems(target), feats)
+
     for step in range(1, a.steps + 1):
         opt.zero_grad()
         out = tcn(x, film_params=gen(torch.cat([emb_in, emb_tg], dim=1)))
         fit = mrstft(out, target)
         cycle = mrstft(tcn(out, film_params=gen(torch.cat([emb_tg, emb_in], dim=1))), x)
         loss = fit + a.lambda_cycle * cycle
+        if encoder is not None:
+            style = cosine_distance_loss(encoder(as_stems(out), feats), style_target)
+            loss = loss + a.style_weight * style
         loss.backward()
         torch.nn.utils.clip_grad_norm_(tcn.parameters(), max_norm=1.0)
         torch.nn.utils.clip_grad_norm_(gen.parameters(), max_norm=1.0)
         opt.step()
-        print(f"step {step} loss {loss.item():.6f} (target {fit.item():.6f}, cycle {cycle.item():.6f})", flush=True)
+        extra = f", style {style.item():.6f}" if encoder is not None else ""
+        print(f"step {step} loss {loss.item():.6f} (target {fit.item():.6f}, cycle {cycle.item():.6f}{extra})", flush=True)
 
 
 if __name__ == "__main__":

@@ -510,6 +510,30 @@ int mst_mrstft_backward(const float* x, const float* y, int rows, int T, int n_r
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Stage A backward: the gradient of the log-mel front end to the waveform (what the style term of the style-transfer
+ * trainer, src/train_style_transfer.py:192-224, needs from the frozen encoder's first stage).
+ * For L = log(mel + 1e-10), mel[m,f] = sum_k fb[k,m] |X[k,f]|^2, X = stft(x) (center / reflect, periodic Hann,
+ * one-sided, F = 1 + T / hop frames) and a cotangent g on L:  grad_x = adjoint STFT of 2 dP X,
+ * dP[k,f] = sum_m fb[k,m] g[m,f] / (mel[m,f] + 1e-10), mel recomputed with the frames (nothing of the forward is kept).
+ * x: dev fp32 [rows][T]; grad_logmel: dev fp32 [rows][n_mels][F] (MST_LOGMEL_REF with rows = B * 8).
+ * n_fft in {1024, 2048}, hop in {n_fft/8, n_fft/4, n_fft/2}, n_mels <= 256, T > n_fft / 2.  window: dev fp32 [n_fft].
+ * The filterbank enters as a per-bin band table built by the caller on the host: band dev int32 [n_fft/2 + 1][2] =
+ * (first mel index, count), band_weight dev fp32 [n_fft/2 + 1][MST_LOGMEL_BAND_MAX] = fb[k][first], fb[k][first + 1];
+ * band_width = the widest count of the table: more than MST_LOGMEL_BAND_MAX is refused (MST_EINVAL), never truncated.
+ * mel_ranges: dev int32 [n_mels][4] = (start, count) of the run of bins whose FIRST mel is m, (start, count) of the run
+ * whose SECOND mel is m -- the transposed view of `band`, for the mel sums (triangular filters: each is one run of bins;
+ * the caller checks that its table has this form).
+ * grad_x: dev [rows][T], every element written (accumulate = 0) or added to (accumulate != 0).
+ * Bit-reproducible (fixed-order overlap-add, no floating-point atomics), stream-ordered, no host sync, no allocation.
+ * ------------------------------------------------------------------------------------------ */
+#define MST_LOGMEL_BAND_MAX 2
+size_t mst_logmel_backward_workspace_bytes(int rows);
+int mst_logmel_backward(const float* x, const float* grad_logmel, int rows, int T, int n_fft, int hop, int n_mels,
+                        const float* window, const int32_t* band, const float* band_weight, int band_width,
+                        const int32_t* mel_ranges, float* grad_x, int accumulate, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Stage C: TCN mixer (eval) -- the style-transfer stage that consumes the embeddings.
  * Replaces: TCNMixer.forward src/tcn_mixer.py:285-321 (input 1x1 conv, num_blocks residual blocks with dilation
  * 2^i, output 1x1 conv + x), ResidualBlock.forward :82-90, FiLMResidualBlock.forward :119-145, CausalConv1d :16-36,

@@ -212,6 +212,9 @@ SYMBOLS = {
     "mst_mrstft_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                       C.POINTER(C.c_void_p), C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_size_t, C.c_void_p]),
+    "mst_logmel_backward_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "mst_logmel_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mst_tcn_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(TcnConfig), C.POINTER(TcnWeights)]),
     "mst_tcn_destroy": (None, [C.c_void_p]),
     "mst_tcn_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_longlong]),

@@ -17,6 +17,15 @@
 // the PADDED signal and computes every frame that touches it (n/hop - 1 frames of halo per 64 chunks); the frames are added
 // into an LDS ring in a fixed order (no floating-point atomics), finished chunks are flushed.  The two n/2-sample borders of
 // the padding go to a small buffer and are folded back into the clip by a second kernel (adjoint of the reflection).
+//
+// Second half of the file: the waveform gradient of the log-mel front end (stage A, melfeat.hip), mst_logmel_backward.
+//   L = log(mel + 1e-10), mel[m,f] = sum_k fb[k,m] |X[k,f]|^2, cotangent g on L:
+//   w = g / (mel + 1e-10) with mel RECOMPUTED from the recomputed |X|^2 (exp(-L) of the saved output missed the parity rule:
+//   stage A's log is the hardware log2, 1e-6 absolute), dP[k,f] = sum_m fb[k,m] w[m,f], G = 2 dP X,
+// and the SAME adjoint STFT: logmel_bwd_kernel is mrstft_bwd_kernel with one signal per frame pair and this per-bin
+// cotangent.  The cotangent tile of a workgroup's frames (n_mels x (chunks + R - 1)) is staged into LDS once; the filterbank
+// enters as a per-bin band table (first mel index, count, up to kBandMax weights: HTK triangles touch at most 2 mels per
+// bin) and, for the mel sums, per mel the two runs of bins that hold it as their first / second mel.
 #include "common.h"
 #include <algorithm>
 
@@ -454,6 +463,240 @@ int mst_mrstft_backward(const float* x, const float* y, int rows, int T, int n_r
   const size_t n = (size_t)rows * T;
   hipLaunchKernelGGL(mrstft_scale_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st, grad_x, n, grad_scale,
                      1.0f / (float)n_res);
+  MST_HIP_CHECK(hipGetLastError());
+  return MST_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Log-mel front end: gradient to the waveform
+namespace {
+
+constexpr int kBandMax = MST_LOGMEL_BAND_MAX;   // mel weights per bin the kernel carries
+constexpr size_t kMaxLds = 160 * 1024;
+
+constexpr int kMelMax = 256, kMelRounds = kMelMax / 64;   // one lane per mel, kMelRounds mels per lane
+
+struct LogmelBwdParams {
+  const float* x;        // [rows][T]
+  const float* g;        // [rows][n_mels][F] cotangent on the log-mel
+  const float* window;
+  const int2* band;      // [N / 2 + 1] (first mel index, count <= kBandMax)
+  const float2* bandw;   // [N / 2 + 1] weights of (first, first + 1), zero where absent
+  const int4* melr;      // [n_mels] bins that hold mel m as their first mel (start, count) and as their second (start, count)
+  float* grad;           // [rows][T]
+  float* border;         // [rows][2][kBorder]
+  int rows, T, hop, lh, R, F, nchunks, cpb, blocks_per_row, accumulate, n_mels, wstride;
+};
+
+template <int N>
+__global__ __launch_bounds__(kThreads) void logmel_bwd_kernel(const LogmelBwdParams p) {
+  using G = Geo<N>;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  Lds<N> l(smem, wave);
+  l.fill(p.window, tid);
+  const int hop = p.hop, lh = p.lh, R = p.R, nslot = kRound + R - 1;
+  for (int i = tid; i < nslot * hop; i += kThreads) l.acc[i] = 0.f;
+  float2* wv = reinterpret_cast<float2*>(l.acc + nslot * hop) + wave * kMelMax;   // this wave's w = g / (mel + 1e-10), frames (A, B)
+  float* gt = l.acc + nslot * hop + 2 * kWaves * kMelMax;   // cotangent tile of this workgroup's frames, [n_mels][wstride]
+  float4* Q = reinterpret_cast<float4*>(l.scr);   // per bin (w0 P_A, w0 P_B, w1 P_A, w1 P_B): the power spectrum times its two mel weights
+  const int row = blockIdx.x / p.blocks_per_row, blk = blockIdx.x % p.blocks_per_row;
+  const int c0 = blk * p.cpb, c1 = min(c0 + p.cpb, p.nchunks);
+  const int fa = max(0, c0 - R + 1), fb = min(p.F - 1, c1 - 1);
+  const int nfr = fb - fa + 1, ws = p.wstride;   // nfr <= cpb + R - 1 <= wstride (<= 0: a tail block no frame reaches)
+  const float* xr = p.x + (size_t)row * p.T;
+  float* gr = p.grad + (size_t)row * p.T;
+  float* bl = p.border + (size_t)row * 2 * kBorder;
+  if (nfr > 0) {   // contiguous runs along f of the (rows, n_mels, F) layout
+    const size_t base = (size_t)row * p.n_mels * p.F + fa;
+    for (int i = tid; i < p.n_mels * nfr; i += kThreads) {
+      const int m = i / nfr, f = i - m * nfr;
+      const size_t at = base + (size_t)m * p.F + f;
+      gt[m * ws + f] = p.g[at];
+    }
+  }
+  int4 mr[kMelRounds];   // the bin ranges of this lane's mels
+#pragma unroll
+  for (int q = 0; q < kMelRounds; ++q) mr[q] = lane + 64 * q < p.n_mels ? p.melr[lane + 64 * q] : make_int4(0, 0, 0, 0);
+  __syncthreads();
+  for (int fr0 = fa; fr0 < c1; fr0 += kRound) {
+    const int gA = fr0 + 2 * wave;
+    const bool hasA = gA <= fb, hasB = gA + 1 <= fb;
+    float2 v[G::NF][G::NCR];
+    // a frame whose cotangent is zero in every bin adds NOTHING (its true gradient is exactly 0, while its half of the packed
+    // inverse transform holds the other frame's rounding residue)
+    bool nzA = false, nzB = false;
+    if (hasA) {   // wave-uniform
+      const int start = gA * hop - N / 2;
+      float2 XA[G::NB], XB[G::NB];
+      load_pair<N>(xr, p.T, start, hop, hasB, l, v, lane);
+      wave_fft<N>(v, l, lane);
+      split_pair<N>(v, l, lane, XA, XB);
+      // mel power of the two frames, recomputed: every bin lays out its power times its two mel weights, one lane per mel adds
+      // up the bins of its triangle (rising half: bins whose second mel it is; falling half: bins whose first) in bin order
+#pragma unroll
+      for (int j = 0; j < G::NB; ++j) {
+        const int k = j == G::NB - 1 ? N / 2 : lane + 64 * j;
+        const float2 bw = p.bandw[k];
+        const float pa = fmaf(XA[j].x, XA[j].x, XA[j].y * XA[j].y), pb = fmaf(XB[j].x, XB[j].x, XB[j].y * XB[j].y);
+        if (j < G::NB - 1 || lane == 0) Q[k] = make_float4(bw.x * pa, bw.x * pb, bw.y * pa, bw.y * pb);
+      }
+      wsync();
+      const float* ga = gt + (gA - fa);
+      const float* gb = ga + (hasB ? 1 : 0);   // (no second frame: no read past the tile)
+#pragma unroll
+      for (int q = 0; q < kMelRounds; ++q) {
+        const int m = lane + 64 * q;
+        if (m < p.n_mels) {
+          float sa = 0.f, sb = 0.f;
+          for (int i = 0; i < mr[q].w; ++i) {
+            const float4 t = Q[mr[q].z + i];
+            sa += t.z, sb += t.w;
+          }
+          for (int i = 0; i < mr[q].y; ++i) {
+            const float4 t = Q[mr[q].x + i];
+            sa += t.x, sb += t.y;
+          }
+          wv[m] = make_float2(ga[m * ws] / (sa + 1e-10f), gb[m * ws] / (sb + 1e-10f));
+        }
+      }
+      wsync();
+      // cotangent of the two spectra G = 2 dP X, packed: conj(H), H = herm(G_A) + i herm(G_B)
+#pragma unroll
+      for (int j = 0; j < G::NB; ++j) {
+        const int k = j == G::NB - 1 ? N / 2 : lane + 64 * j;
+        const int2 bd = p.band[k];
+        const float2 bw = p.bandw[k];
+        float da = 0.f, db = 0.f;
+        if (bd.y > 0) {
+          const float2 w = wv[bd.x];
+          da = bw.x * w.x, db = bw.x * w.y;
+        }
+        if (bd.y > 1) {
+          const float2 w = wv[bd.x + 1];
+          da = fmaf(bw.y, w.x, da), db = fmaf(bw.y, w.y, db);
+        }
+        da *= 2.f;
+        db = hasB ? 2.f * db : 0.f;   // (no frame: no cotangent)
+        const float ar = da * XA[j].x, ai = da * XA[j].y, br = db * XB[j].x, bi = db * XB[j].y;
+        nzA |= ar != 0.f || ai != 0.f;
+        nzB |= br != 0.f || bi != 0.f;
+        if (j == G::NB - 1) {
+          if (lane == 0) l.scr[pad8(N / 2)] = make_float2(ar, -br);
+        } else {
+          if (k == 0) {
+            l.scr[pad8(0)] = make_float2(ar, -br);
+          } else {
+            l.scr[pad8(k)] = make_float2(0.5f * (ar - bi), -0.5f * (ai + br));
+            l.scr[pad8(N - k)] = make_float2(0.5f * (ar + bi), 0.5f * (ai - br));
+          }
+        }
+      }
+      wsync();
+#pragma unroll
+      for (int r = 0; r < G::REGS; ++r) v[r / G::NCR][r % G::NCR] = l.scr[pad8(in_idx<N>(r, lane))];
+      wave_fft<N>(v, l, lane);   // = g_A[n] - i g_B[n]
+      nzA = __any(nzA), nzB = __any(nzB);
+    }
+    // overlap-add in a fixed order: in phase ph the frames fr0 + ph (mod R) -- R frames apart, they do not overlap
+    for (int ph = 0; ph < R; ++ph) {
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const int g = gA + e;
+        if ((e ? hasB && nzB : hasA && nzA) && ((g - fr0) & (R - 1)) == ph) {   // wave-uniform
+#pragma unroll
+          for (int r = 0; r < G::REGS; ++r) {
+            const int nb = out_idx<N>(r, 0);   // lane + 64 q stays inside one chunk: hop is a multiple of 64
+            const int slot = (g + (nb >> lh)) % nslot;
+            const float2 z = v[r / G::NCR][r % G::NCR];
+            l.acc[slot * hop + (nb & (hop - 1)) + lane] += l.win[nb + lane] * (e ? -z.y : z.x);
+          }
+        }
+      }
+      __syncthreads();
+    }
+    // chunks [fr0, fr0 + kRound) are complete: no later frame reaches them
+    const int nfl = min(fr0 + kRound, c1) - fr0;
+    for (int i = tid; i < nfl * hop; i += kThreads) {
+      const int c = fr0 + (i >> lh), off = i & (hop - 1);
+      float* a = l.acc + (c % nslot) * hop + off;
+      const float val = *a;
+      *a = 0.f;
+      const int pp = c * hop + off;
+      if (c >= c0 && pp < p.T + N) {
+        const int t = pp - N / 2;
+        if (t < 0) bl[-t - 1] = val;
+        else if (t >= p.T) bl[kBorder + t - p.T] = val;
+        else gr[t] = p.accumulate ? gr[t] + val : val;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+template <int N>
+size_t logmel_bwd_lds(int R, int hop, int n_mels, int cpb) {
+  return Geo<N>::kLds + ((size_t)(kRound + R - 1) * hop + 2 * kWaves * kMelMax + (size_t)n_mels * ((cpb + R - 1) | 1)) * sizeof(float);
+}
+
+template <int N>
+int launch_logmel_bwd(LogmelBwdParams& p, hipStream_t st) {
+  // a workgroup owns 64 hop-sized chunks; fewer where the cotangent tile of 64 + R - 1 frames would not fit the CU's LDS next to
+  // the transform's tables (n_fft = 2048 with more than ~118 mels)
+  p.cpb = kChunksPerBlock;
+  while (p.cpb > 8 && logmel_bwd_lds<N>(p.R, p.hop, p.n_mels, p.cpb) > kMaxLds) p.cpb /= 2;
+  const size_t lds = logmel_bwd_lds<N>(p.R, p.hop, p.n_mels, p.cpb);
+  MST_REQUIRE(lds <= kMaxLds, "mst_logmel_backward: LDS %zu B exceeds 160 KiB (n_fft=%d hop=%d n_mels=%d)", lds, N, p.hop, p.n_mels);
+  p.wstride = (p.cpb + p.R - 1) | 1;
+  p.blocks_per_row = (p.nchunks + p.cpb - 1) / p.cpb;
+  const long long grid = (long long)p.rows * p.blocks_per_row;
+  MST_REQUIRE(grid < (1LL << 31), "mst_logmel_backward: %lld workgroups", grid);
+  MST_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_bwd_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((logmel_bwd_kernel<N>), dim3((unsigned)grid), dim3(kThreads), lds, st, p);
+  MST_HIP_CHECK(hipGetLastError());
+  return MST_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mst_logmel_backward_workspace_bytes(int rows) {
+  return rows > 0 ? mst::align_up((size_t)rows * 2 * kBorder * sizeof(float), 256) : 0;
+}
+
+int mst_logmel_backward(const float* x, const float* grad_logmel, int rows, int T, int n_fft, int hop, int n_mels,
+                        const float* window, const int32_t* band, const float* band_weight, int band_width,
+                        const int32_t* mel_ranges, float* grad_x, int accumulate, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+  MST_REQUIRE(x && grad_logmel && window && band && band_weight && mel_ranges && grad_x, "mst_logmel_backward: NULL argument");
+  MST_REQUIRE(n_fft == 1024 || n_fft == 2048, "mst_logmel_backward: n_fft=%d is not 1024 or 2048", n_fft);
+  MST_REQUIRE(hop == n_fft / 8 || hop == n_fft / 4 || hop == n_fft / 2, "mst_logmel_backward: hop=%d is not n_fft/8, /4 or /2 (n_fft=%d)",
+              hop, n_fft);
+  MST_REQUIRE(n_mels >= 1 && n_mels <= kMelMax, "mst_logmel_backward: n_mels=%d outside 1..%d", n_mels, kMelMax);
+  MST_REQUIRE(rows > 0 && rows <= (1 << 20) && T > 0 && T < (1 << 30), "mst_logmel_backward: bad sizes rows=%d T=%d", rows, T);
+  MST_REQUIRE(T > n_fft / 2, "mst_logmel_backward: T=%d needs more than n_fft/2 = %d samples (reflect padding)", T, n_fft / 2);
+  MST_REQUIRE(band_width >= 1 && band_width <= kBandMax,
+              "mst_logmel_backward: the filterbank's widest band has %d non-zero mel weights on one bin, the kernel carries %d "
+              "(HTK triangles have 2); the table is refused, not truncated", band_width, kBandMax);
+  const size_t need = mst_logmel_backward_workspace_bytes(rows);
+  if (!workspace || workspace_bytes < need)
+    return mst::fail(MST_ENOMEM, "mst_logmel_backward: workspace %zu B < required %zu B", workspace_bytes, need);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  LogmelBwdParams p;
+  p.x = x, p.g = grad_logmel, p.window = window;
+  p.band = reinterpret_cast<const int2*>(band), p.bandw = reinterpret_cast<const float2*>(band_weight);
+  p.melr = reinterpret_cast<const int4*>(mel_ranges);
+  p.grad = grad_x, p.border = reinterpret_cast<float*>(workspace);
+  p.rows = rows, p.T = T, p.hop = hop, p.lh = log2_exact(hop), p.R = n_fft / hop, p.F = 1 + T / hop;
+  p.nchunks = (int)(((long long)T + n_fft + hop - 1) / hop);
+  p.accumulate = accumulate != 0, p.n_mels = n_mels;
+  p.cpb = p.blocks_per_row = p.wstride = 0;
+  if (int rc = n_fft == 1024 ? launch_logmel_bwd<1024>(p, st) : launch_logmel_bwd<2048>(p, st)) return rc;
+  hipLaunchKernelGGL(mrstft_fold_kernel, dim3(rows), dim3(256), 0, st, grad_x, p.border, T, n_fft / 2);
   MST_HIP_CHECK(hipGetLastError());
   return MST_OK;
 }

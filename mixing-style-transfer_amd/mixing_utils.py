@@ -63,6 +63,56 @@ def melscale_fbanks_htk(n_freqs: int, n_mels: int, sample_rate: int) -> torch.Te
     return torch.max(torch.zeros(1), torch.min(lower, upper))
 
 
+LOGMEL_BAND_MAX = 2   # include/mst.h MST_LOGMEL_BAND_MAX: mel weights per bin the log-mel backward kernel carries
+
+
+def mel_band_table(fb: torch.Tensor):
+    """Per-bin band table of a mel filterbank `fb` (n_freqs, n_mels), the form in which the log-mel backward kernel reads it:
+    -> (first (n_freqs,) int32, count (n_freqs,) int32, weights (n_freqs, width) fp32) with
+    weights[k, i] = fb[k, first[k] + i] for i < count[k] (zero beyond), first/count spanning bin k's non-zero mels
+    (count 0, first 0: a bin no filter touches), width = max(count, 1).  Scattering the table back gives `fb` bit for bit.
+    HTK triangles give width 2; a wider table is built faithfully here and refused by the kernel's entry point."""
+    fb = fb.detach().float().cpu().contiguous()
+    nz = fb.view(torch.int32) != 0   # by bit pattern: torchaudio's table holds a -0.0 (bin 0), which is kept
+    n_freqs, n_mels = fb.shape
+    idx = torch.arange(n_mels).expand(n_freqs, n_mels)
+    any_nz = nz.any(dim=1)
+    first = torch.where(nz, idx, torch.full_like(idx, n_mels)).min(dim=1).values
+    last = torch.where(nz, idx, torch.full_like(idx, -1)).max(dim=1).values
+    first = torch.where(any_nz, first, torch.zeros_like(first))
+    count = torch.where(any_nz, last - first + 1, torch.zeros_like(first))
+    width = max(int(count.max()), 1)
+    cols = first[:, None] + torch.arange(width)[None, :]
+    live = torch.arange(width)[None, :] < count[:, None]
+    weights = torch.where(live, fb.gather(1, cols.clamp(max=n_mels - 1)), torch.zeros(()))
+    return first.to(torch.int32), count.to(torch.int32), weights.contiguous()
+
+
+def mel_bin_ranges(first, count, n_mels):
+    """The transposed view of a band table of width <= 2, for the mel sums of the log-mel backward kernel: (n_mels, 4) int32 =
+    (start, count) of the bins whose FIRST mel is m, (start, count) of the bins whose SECOND mel is m.  Triangular filters give
+    one run of bins each; a table where such a set is not one run raises ValueError (the kernel walks runs)."""
+    out = torch.zeros(n_mels, 4, dtype=torch.int32)
+    for col, (mel_of_bin, live) in enumerate(((first, count >= 1), (first + 1, count >= 2))):
+        for m in range(n_mels):
+            ks = ((mel_of_bin == m) & live).nonzero().squeeze(1)
+            if ks.numel():
+                if int(ks[-1] - ks[0]) + 1 != ks.numel():
+                    raise ValueError(f"mel filter {m} does not cover one contiguous run of bins: the log-mel backward kernel takes "
+                                     "triangular (band-limited, contiguous) filters")
+                out[m, 2 * col], out[m, 2 * col + 1] = int(ks[0]), ks.numel()
+    return out
+
+
+def band_table_to_dense(first, count, weights, n_mels):
+    """Inverse of `mel_band_table`: the dense (n_freqs, n_mels) filterbank."""
+    fb = torch.zeros(first.shape[0], n_mels, dtype=weights.dtype)
+    for i in range(weights.shape[1]):
+        rows = (count > i).nonzero().squeeze(1)
+        fb[rows, (first[rows] + i).long()] = weights[rows, i]
+    return fb
+
+
 class LogMel:
     """A log-mel batch in one of the ENCODER-INTERNAL channel-minor layouts that stage A writes directly (include/mst.h
     MST_LOGMEL_CM32 / CM16): `data` (B, frames, n_mels, 8) fp32, or float16 high parts with the low parts in `lo`;
@@ -257,7 +307,9 @@ class MixingFeatureExtractor:
         return torch.where(is_deferred(features), f, features.to(f.dtype))
 
     def extract_all_features(self, stems_dict):
-        """stems_dict {stem: (2,T)} -> (feature_dim,)  [reference]; {stem: (B,2,T)} -> (B, feature_dim)."""
+        """stems_dict {stem: (2,T)} -> (feature_dim,)  [reference]; {stem: (B,2,T)} -> (B, feature_dim).
+        The features carry no autograd history, also when a stem does: they condition the encoder as constants (the reference
+        comments "no grad for feature extractor" at train_style_transfer.py:205)."""
         batched = next(iter(stems_dict.values())).dim() == 3
         _, f = self.plan().forward_stems(stems_dict, False, True)
         return f if batched else f[0]

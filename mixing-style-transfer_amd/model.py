@@ -12,6 +12,10 @@ Forward paths
     autograd Function (`_HipTrunk`); pooling head and FiLM MLP in csrc/head.hip.  A call the hand-written trunk cannot take
     RAISES (no silent library path); the library paths are explicit opt-ins: `train_backend = "torch"` runs the whole encoder on
     PyTorch-ROCm autograd (the path the gradients are tested against), `"hip-or-torch"` warns once per reason and falls back.
+  * gradient to the WAVEFORM (a stem requires grad and grad is enabled -- the style term of the style-transfer trainer through
+    a frozen encoder): stage A forward and backward in HIP (`_LogMelHip`, `mst_logmel_backward`), the conv trunk on
+    PyTorch-ROCm autograd with `encoder_backend = "torch"`; `encoder_backend = "hip"` raises (the hand-written eval trunk has
+    no input gradient yet).  The mixing features of the same launch are constants.
 """
 import ctypes as C
 
@@ -23,8 +27,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .mixing_utils import (STEMS, LogMel, MelFeatPlan, detailed_bins_for_feature_dim, hann_window, is_deferred,
-                           melscale_fbanks_htk, stems_to_tensor)
+from .mixing_utils import (LOGMEL_BAND_MAX, STEMS, LogMel, MelFeatPlan, detailed_bins_for_feature_dim, hann_window, is_deferred,
+                           mel_band_table, mel_bin_ranges, melscale_fbanks_htk, stems_to_tensor)
 
 
 class _Buf(nn.Module):
@@ -43,14 +47,113 @@ class _MelTransform(nn.Module):
         self.mel_scale = _Buf("fb", melscale_fbanks_htk(n_fft // 2 + 1, n_mels, sample_rate))
 
 
+class _LogMelHip(torch.autograd.Function):
+    """Stage A with the gradient to the waveform.  Forward = the stage-A launch in the reference layout (the same launch as
+    the no-grad path: bit-equal values; the mixing features it can emit next to the log-mel are returned as constants).
+    Backward = `mst_logmel_backward` (csrc/mrstft.hip): recomputes the frames and their mel power (only the stems are saved)
+    and runs the adjoint STFT with a fixed summation order (bit-reproducible)."""
+
+    @staticmethod
+    def forward(ctx, pre, plan, want_feats, vocals, bass, drums, other):
+        stems = (vocals, bass, drums, other)
+        lm, feats = plan.forward_stems({s: q.detach() for s, q in zip(STEMS, stems)}, True, want_feats)
+        ctx.pre, ctx.shape = pre, vocals.shape
+        ctx.save_for_backward(*stems)
+        if feats is None:
+            feats = lm.new_empty(0)
+        ctx.mark_non_differentiable(feats)
+        return lm, feats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_feats):
+        stems = ctx.saved_tensors
+        pre = ctx.pre
+        B, _, M, Fr = g.shape
+        T = stems[0].shape[-1]
+        x = torch.cat([q.reshape(B, 2, T) for q in stems], dim=1)   # (B, 8, T), the row order of the log-mel
+        g = g.contiguous().float()
+        grad = torch.empty_like(x)
+        win, band, bandw, width, melr = pre._grad_tables(x.device)
+        L = _lib.lib()
+        need = L.mst_logmel_backward_workspace_bytes(B * 8)
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(L.mst_logmel_backward(_lib.dptr(x), _lib.dptr(g), B * 8, T, pre.n_fft, pre.hop_length, M, _lib.dptr(win),
+                                             _lib.dptr(band), _lib.dptr(bandw), width, _lib.dptr(melr), _lib.dptr(grad), 0,
+                                             _lib.dptr(ws), need, _lib.stream_ptr(x.device)), "mst_logmel_backward")
+        return (None, None, None) + tuple(grad[:, 2 * i:2 * i + 2].reshape(ctx.shape) if ctx.needs_input_grad[3 + i] else None
+                                          for i in range(4))
+
+
 class MelSpectrogramPreprocessor(nn.Module):
-    """Dict of 4 stems, each (B, 2, T) -> log-mel (B, 8, n_mels, frames).  reference src/model.py:17-67"""
+    """Dict of 4 stems, each (B, 2, T) -> log-mel (B, 8, n_mels, frames).  reference src/model.py:17-67
+
+    With grad enabled and a stem that requires grad the result carries the gradient to the waveform (`_LogMelHip`: stage A
+    forward and backward in HIP; fp32 CUDA stems, n_fft in {1024, 2048}, hop in {n_fft/8, n_fft/4, n_fft/2}, n_mels <= 256,
+    T > n_fft/2 -- anything else raises RuntimeError naming the reason).  A call where nothing requires grad is the plain
+    stage-A launch."""
 
     def __init__(self, sample_rate=44100, n_fft=1024, hop_length=256, n_mels=128):
         super().__init__()
         self.sample_rate, self.n_fft, self.hop_length, self.n_mels = sample_rate, n_fft, hop_length, n_mels
         self.mel_transform = _MelTransform(sample_rate, n_fft, n_mels)
         self._plans = {}
+        self._grad_tabs = {}
+
+    @staticmethod
+    def wants_grad(stems_dict):
+        return torch.is_grad_enabled() and any(torch.is_tensor(q) and q.requires_grad for q in stems_dict.values())
+
+    def _grad_refusal(self, stems_dict):
+        """Why the waveform gradient cannot be computed for this call (None = it can)."""
+        parts = [stems_dict[s] for s in STEMS]
+        n, h = self.n_fft, self.hop_length
+        for s, q in zip(STEMS, parts):
+            if not q.is_cuda:
+                return f"libmst kernels need CUDA (HIP) tensors and there is no CPU fallback, got '{s}' on {q.device}"
+            if q.dtype != torch.float32:
+                return f"the waveform gradient is fp32, got '{s}' of {q.dtype}"
+            if q.shape != parts[0].shape or q.dim() not in (2, 3) or q.shape[-2] != 2:
+                return f"stems of one shape (B, 2, T) or (2, T) are needed, got {[tuple(t.shape) for t in parts]}"
+        if n not in (1024, 2048):
+            return f"the backward kernel has n_fft 1024 and 2048, got n_fft={n}"
+        if h not in (n // 8, n // 4, n // 2):
+            return f"the backward kernel needs hop_length in (n_fft/8, n_fft/4, n_fft/2), got hop_length={h} for n_fft={n}"
+        if self.n_mels > 256:
+            return f"the backward kernel takes n_mels <= 256, got {self.n_mels}"
+        if parts[0].shape[-1] <= n // 2:
+            return f"T > n_fft/2 = {n // 2} samples are needed (reflect padding), got T = {parts[0].shape[-1]}"
+        if parts[0].numel() == 0:
+            return "empty input"
+        return None
+
+    def _grad_tables(self, device):
+        """Window and per-bin band table of the module's OWN buffers on `device` (a loaded checkpoint's tables are honoured)."""
+        key = str(device)
+        if key not in self._grad_tabs:
+            first, count, weights = mel_band_table(self.mel_transform.mel_scale.fb)
+            width = weights.shape[1]
+            w2 = torch.zeros(weights.shape[0], max(width, LOGMEL_BAND_MAX))
+            w2[:, :width] = weights   # the kernel's row stride; a wider table is passed on as it is and refused there
+            melr = mel_bin_ranges(first, count, self.n_mels) if width <= LOGMEL_BAND_MAX else torch.zeros(self.n_mels, 4, dtype=torch.int32)
+            self._grad_tabs[key] = (self.mel_transform.spectrogram.window.detach().float().to(device).contiguous(),
+                                    torch.stack([first, count], dim=1).contiguous().to(device), w2.contiguous().to(device), width,
+                                    melr.to(device))
+        return self._grad_tabs[key]
+
+    def forward_with_grad(self, stems_dict, plan=None, want_feats=False):
+        """(log-mel with the gradient to the stems, mixing features of the same launch as constants or None)."""
+        why = self._grad_refusal(stems_dict)
+        if why is None:
+            try:   # built here, not in backward: a filterbank the kernel cannot walk is refused before any launch
+                self._grad_tables(stems_dict[STEMS[0]].device)
+            except ValueError as e:
+                why = str(e)
+        if why:
+            raise RuntimeError("MelSpectrogramPreprocessor: no gradient to the waveform for this call: " + why)
+        lm, feats = _LogMelHip.apply(self, plan or self.plan(), bool(want_feats), *[stems_dict[s] for s in STEMS])
+        return lm, (feats if want_feats else None)
 
     def plan(self, detailed_bins=0) -> MelFeatPlan:
         """Stage-A plan; `detailed_bins` selects the feature layout the same launch can emit next to the log-mel."""
@@ -63,8 +166,11 @@ class MelSpectrogramPreprocessor(nn.Module):
     def _load_from_state_dict(self, *a, **k):
         super()._load_from_state_dict(*a, **k)
         self._plans = {}
+        self._grad_tabs = {}
 
     def forward(self, stems_dict):
+        if self.wants_grad(stems_dict):
+            return self.forward_with_grad(stems_dict)[0]
         lm, _ = self.plan().forward_stems(stems_dict, True, False)
         return lm
 
@@ -1081,8 +1187,19 @@ class MixingStyleEncoder(nn.Module):
             want = self._train_encoder().train_layout()
             if plan.supports_layout(want):
                 layout, want_lo = want, self._train_encoder().train_mode != 1   # (f16 mode: the high parts alone)
-        with torch.no_grad():
-            logmel, feats = plan.forward_stems(stems_dict, True, has_feats, layout, want_absmax=layout == _lib.LOGMEL_CM16, want_lo=want_lo)
+        if pre.wants_grad(stems_dict):
+            # the style term of the style-transfer trainer (src/train_style_transfer.py:192-224): the gradient of the embedding to
+            # the WAVEFORM.  Stage A forward and backward run in HIP (_LogMelHip); the conv trunk, FiLM and the head on
+            # PyTorch-ROCm autograd.  The mixing features of the same launch condition the encoder as constants.
+            if not (self.encoder_backend == "torch" or (self.training and auto and self.train_backend == "torch")):
+                raise RuntimeError("MixingStyleEncoder: a stem requires grad, but the hand-written HIP trunk (encoder_backend='hip') "
+                                   "has no gradient to its input yet; encoder_backend=\"torch\" runs stage A forward and backward in "
+                                   "HIP and the conv trunk on PyTorch-ROCm autograd (detach the stems if no waveform gradient is wanted)")
+            logmel, feats = pre.forward_with_grad(stems_dict, plan, has_feats)
+        else:
+            with torch.no_grad():
+                logmel, feats = plan.forward_stems(stems_dict, True, has_feats, layout, want_absmax=layout == _lib.LOGMEL_CM16,
+                                                   want_lo=want_lo)
         mf = mixing_features.to(logmel.device)
         if feats is not None:
             mf = torch.where(is_deferred(mf), feats.to(mf.dtype), mf)
