@@ -838,11 +838,7 @@ int mst_aug_apply_from(const mst_aug_clip* decisions, int B, int T, const float*
     MST_HIP_CHECK(hipMemsetAsync(ws + L.lb + 64, 0xFF, L.lb_bytes - 64, st));   // every carry word = kCarryEmpty
     hipLaunchKernelGGL(aug_active_kernel, dim3(1), dim3(64), 0, st, ddec, B, cp.act, in_place ? 0 : 1);
     hipLaunchKernelGGL(aug_powers_kernel, dim3(B * 8), dim3(64), 0, st, ddec, cp.pow);
-    static unsigned long long chain_attr = 0;   // per-device bit mask: the dynamic-LDS limit belongs to the device
-    if (mst::first_use_on_device(chain_attr))
-      MST_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(aug_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)sizeof(ChainLds)));
-    hipLaunchKernelGGL(aug_chain_kernel, dim3(B * 8 * L.nseg), dim3(kFT), sizeof(ChainLds), st, cp);
+    MST_HIP_CHECK(mst::launch_lds<aug_chain_kernel>(dim3(B * 8 * L.nseg), dim3(kFT), sizeof(ChainLds), st, cp));
   }
   MST_HIP_CHECK(hipGetLastError());
   if (any_rev) {
@@ -855,12 +851,7 @@ int mst_aug_apply_from(const mst_aug_clip* decisions, int B, int T, const float*
     hipLaunchKernelGGL((rev_fft_kernel<0>), dim3((L.NP + 3) / 4, B), dim3(256), 0, st, rp);
     hipLaunchKernelGGL((rev_fft_kernel<1>), dim3((L.NX + 3) / 4, B), dim3(256), 0, st, rp);   // (+ the stems' energy partials)
     hipLaunchKernelGGL(aug_energy_final_kernel, dim3(B), dim3(64), 0, st, ddec, epart, prop, T, L.NX);
-    static unsigned long long rev_attr = 0;   // per-device bit mask: the dynamic-LDS limit belongs to the device
-    if (mst::first_use_on_device(rev_attr))
-      MST_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(rev_mac_ifft_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RevLds)));
-    hipLaunchKernelGGL(rev_mac_ifft_kernel, dim3((L.nj + kRevWaves - 1) / kRevWaves, B), dim3(kRevWaves * 64), sizeof(RevLds), st, rp);
-    MST_HIP_CHECK(hipGetLastError());
+    MST_HIP_CHECK(mst::launch_lds<rev_mac_ifft_kernel>(dim3((L.nj + kRevWaves - 1) / kRevWaves, B), dim3(kRevWaves * 64), sizeof(RevLds), st, rp));
   }
   return MST_OK;
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -15,12 +16,13 @@ namespace mst {
 char* err_buf();
 int fail(int code, const char* fmt, ...);
 
-#define MST_HIP_CHECK(expr)                                                                   \
+// (variadic: the commas of a template argument list split `expr`)
+#define MST_HIP_CHECK(...)                                                                    \
   do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
+    hipError_t e_ = (__VA_ARGS__);                                                            \
     if (e_ != hipSuccess)                                                                     \
-      return ::mst::fail(MST_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),     \
-                         __FILE__, __LINE__);                                                 \
+      return ::mst::fail(MST_EHIP, "%s failed: %s (%s:%d)", #__VA_ARGS__,                     \
+                         hipGetErrorString(e_), __FILE__, __LINE__);                          \
   } while (0)
 
 #define MST_REQUIRE(cond, ...)                                                                \
@@ -30,15 +32,24 @@ int fail(int code, const char* fmt, ...);
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// true the first time a call site runs on the CURRENT device: hipFuncSetAttribute (dynamic-LDS limit) is a per-device
-// setting, so a process that drives several GPUs has to repeat it on each of them.  `mask` is the call site's static.
-inline bool first_use_on_device(unsigned long long& mask) {
+// THE launch of a kernel that uses dynamic LDS: raises the kernel's dynamic-LDS limit when `lds` exceeds what this process
+// already set, then launches.  The limit (hipFuncAttributeMaxDynamicSharedMemorySize) is a per-device attribute of ONE
+// kernel instantiation, so the record lives here, keyed on the kernel: a launch cannot be written without it.  No default
+// limit is assumed (the record starts at 0).  Two threads racing on a first launch both set the attribute, harmlessly.
+constexpr int kLdsLimitDevices = 64;   // devices with a record; beyond them the attribute is set on every launch
+template <auto Kernel, typename... Args>
+hipError_t launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+  static std::atomic<size_t> limits[kLdsLimitDevices];   // (zero-initialised)
   int d = 0;
   (void)hipGetDevice(&d);
-  const unsigned long long bit = 1ull << (d & 63);
-  if (mask & bit) return false;
-  mask |= bit;
-  return true;
+  std::atomic<size_t>* limit = d >= 0 && d < kLdsLimitDevices ? &limits[d] : nullptr;
+  if (!limit || lds > limit->load(std::memory_order_relaxed)) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    if (limit) limit->store(lds, std::memory_order_relaxed);
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+  return hipGetLastError();
 }
 
 template <typename T>

@@ -333,6 +333,7 @@ struct ConvGeom {
   static constexpr int PATCH = (4 * C::PR * C::PC + 3) / 4 * 4;                 // floats per wave patch
   static constexpr int NPF = (4 * C::PR * C::RL + 63) / 64;                     // patch prefetches per lane
   static constexpr int NCV = C::RL >= 64 ? C::RL / 64 : 1;                      // column variants of the loader
+  static constexpr size_t kLds = (size_t)(2 * WBP + kConvWaves * PATCH) * sizeof(float);   // conv_kernel: [2][WBP] + a patch per wave
 };
 
 template <int LAYER, int SUB, int MODE = 0>
@@ -756,6 +757,7 @@ struct RowTiles {
   // tile) of k-group 0 and the same + 16 of k-group 1 fall into disjoint banks
   static constexpr int CP = 304;
   static constexpr int PATCH = 4 * CP;
+  static constexpr size_t kLds = (size_t)(2 * ConvGeom<2, 2>::WBP + kConvWaves * PATCH) * sizeof(float);   // conv2_rows_kernel
 };
 
 __global__ __launch_bounds__(kConvThreads) void conv2_rows_kernel(const ConvParams p) {
@@ -768,7 +770,7 @@ __global__ __launch_bounds__(kConvThreads) void conv2_rows_kernel(const ConvPara
   constexpr int NPIECE = NPFK + NWF, PPT = (NPIECE + 48) / 49;    // prefetch pieces, pieces issued per tap
   static_assert(MT == C::MT && (R::PR - 1) * PC + PC <= 256 && R::FR * 16 <= 256, "4 pieces of 64 lanes cover a channel of either kind");
   static_assert((R::FR - 1) * PC + R::FC <= CP && CP % 32 == 16, "channel pitch, see RowTiles");
-  static_assert((size_t)(2 * WBP + kConvWaves * R::PATCH) * sizeof(float) <= 160 * 1024, "conv2_rows_kernel must fit one CU's LDS");
+  static_assert(R::kLds <= 160 * 1024, "conv2_rows_kernel must fit one CU's LDS");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -985,6 +987,8 @@ __global__ __launch_bounds__(kConvThreads) void conv2_rows_kernel(const ConvPara
 // LAY 1: channel-minor log-mel [B][F][M][8] (MST_LOGMEL_CM32): a frame of the patch -- 8 mel rows x 8 channels -- is 256
 //        contiguous bytes; a lane loads 16-byte units (frame, row, half = 4 channels), 12 per tile, every lane busy, and
 //        scatters them into the same channel-major LDS patch (4 ds_write_b32 per unit, 2-way bank conflicts at most).
+template <int SUB>   // dynamic LDS: the band's weights [2][49 * NT * 64] + an 8-channel patch per wave
+constexpr size_t kConv1ResidentLds = (size_t)(2 * 49 * CC<1, SUB>::NT * 64 + kConvWaves * 8 * CC<1, SUB>::PR * CC<1, SUB>::PC) * sizeof(float);
 template <int SUB, int MODE = 0, int LAY = 0>
 __global__ __launch_bounds__(kConvThreads) void conv1_resident_kernel(const ConvParams p) {
   using C = CC<1, SUB>;
@@ -1632,6 +1636,8 @@ constexpr int kF16Steps = 13;         // ceil(49 taps / 4)
 // LAY 2: the log-mel arrives from stage A as float16 hi / lo planes, channel-minor [B][F][M][8] (MST_LOGMEL_CM16): a patch
 //        position IS one 16-byte vector of the LDS image -- 6 (+ 6 low-part) loads and as many ds_write_b128 per tile, no
 //        conversion, the same bits as LAY 0 produces.
+template <int SUB>   // dynamic LDS in 16-byte vectors: the band's weights [step][nt][hi/lo][lane] + a hi and a lo patch per wave
+constexpr size_t kConv1F16Lds = (size_t)(kF16Steps * CC<1, SUB>::NT * 2 * 64 + kConvWaves * 2 * CC<1, SUB>::PR * CC<1, SUB>::PC) * 16;
 template <int SUB, int TERMS, int MODE = 0, int LAY = 0>
 __global__ __launch_bounds__(kConvThreads) void conv1_f16x3_kernel(const ConvParams p, const h16x8* __restrict__ wfrag16,
                                                                   _Float16* __restrict__ out_hi, _Float16* __restrict__ out_lo) {
@@ -1953,6 +1959,9 @@ constexpr int kF16eRS = 48, kF16eOdd = 4 * kF16eRS + 8, kF16ePatch = kF16eOdd + 
 // <= 168 registers: the third wave covers what two leave open -- per tile a wave has 2240 cycles of MFMAs and about as many of
 // staging, epilogue and tile bookkeeping).
 template <int TERMS> constexpr int kF16eWaves = TERMS == 1 ? 12 : 8;
+template <int TERMS>   // dynamic LDS in 16-byte units: the staged weights and one patch per wave, hi (and lo: TERMS 3) each
+constexpr size_t kConv1F16eLds = (size_t)(TERMS == 3 ? 2 : 1) * (kF16StepsE * CC<1, 2>::NT * 64 + kF16eWaves<TERMS> * kF16ePatch) * 16;
+static_assert(kConv1F16eLds<3> <= 160 * 1024, "conv1_f16e_kernel<3> must fit one CU's LDS");
 template <int TERMS>
 __global__ __launch_bounds__(kF16eWaves<TERMS> * 64) void conv1_f16e_kernel(const ConvParams p, const h16x8* __restrict__ wfrag16,
                                                                  _Float16* __restrict__ out_hi, _Float16* __restrict__ out_lo) {
@@ -2224,6 +2233,8 @@ __global__ __launch_bounds__(kF16eWaves<TERMS> * 64) void conv1_f16e_kernel(cons
 // MODE 1 (training forward, TERMS = 1): raw output + bias in the 8 x 8-tile accumulator order and the batch-statistics
 // sums over the valid positions, as conv_kernel<2, 2, 1> leaves them (tiles past the last row are computed, not stored
 // in the sums: f16 MFMAs are cheap enough that the 2-row strip kernel of the fp32 path is not needed).
+// dynamic LDS in 16-byte vectors: room for a hi/lo weight chunk [step][4 nt][hi/lo][lane] + a hi and a lo 14 x 14 patch per wave
+constexpr size_t kConv2F16Lds = (size_t)(kF16Steps * 4 * 2 * 64 + kConvWaves * 2 * 14 * 14) * 16;
 template <int TERMS, int MODE = 0>
 __global__ __launch_bounds__(kConvThreads) void conv2_f16x3_kernel(const ConvParams p, const h16x8* __restrict__ in_hi,
                                                                   const h16x8* __restrict__ in_lo,
@@ -2686,14 +2697,8 @@ __global__ __launch_bounds__(512) void proj_kernel(const ProjParams p) {
 }
 
 hipError_t launch_attn_scores(const AttnParams& ap, hipStream_t st) {
-  static unsigned long long attr = 0;   // per-device bit mask: the attribute belongs to the device
-  if (mst::first_use_on_device(attr)) {
-    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_scores_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnLds);
-    if (err != hipSuccess) return err;
-  }
   const int mblocks = (ap.B * ap.W + 16 * kAttnMT - 1) / (16 * kAttnMT);
-  hipLaunchKernelGGL(attn_scores_kernel, dim3(mblocks, kAttnHalves), dim3(256), kAttnLds, st, ap);
-  return hipGetLastError();
+  return mst::launch_lds<attn_scores_kernel>(dim3(mblocks, kAttnHalves), dim3(256), kAttnLds, st, ap);
 }
 
 void launch_proj(const ProjParams& pj, hipStream_t st) {
@@ -2713,6 +2718,9 @@ void launch_proj(const ProjParams& pj, hipStream_t st) {
 // Reads the weights from the MFMA fragment table (conv_fragments: [cin / 4][tap][n / 16][lane = 16 (cin % 4) + n % 16]).
 // ------------------------------------------------------------------------------------------
 constexpr int kGenCols = 8, kGenPC = 5 * kGenCols + 6;
+constexpr size_t conv1_generic_lds(int split_size) {   // the band's weights + the whole 8-channel input patch
+  return (size_t)(392 * 32 + 8 * (split_size + 6) * kGenPC) * sizeof(float);
+}
 __global__ __launch_bounds__(256) void conv1_generic_kernel(const ConvParams p, int sub) {
   extern __shared__ __attribute__((aligned(16))) float gsm[];
   float* wl = gsm;                    // [392 (cin, tap)][32 cout]
@@ -3768,31 +3776,99 @@ __global__ void dgrad_fragments_kernel(const float* w, float* f, int nsub, int w
   f[((size_t)b * 16 + ch) * wchp + ((size_t)tap * 2 + n) * 64 + lane] = w[(((size_t)b * 64 + co) * 32 + ci) * 49 + (48 - tap)];
 }
 
-template <int LAYER, int SUB>
+template <int LAYER, int SUB, int MODE = 0>
 hipError_t launch_conv(const ConvParams& cp, int grid, hipStream_t st) {
-  using GEO = ConvGeom<LAYER, SUB>;
-  const size_t lds = (size_t)(2 * GEO::WBP + kConvWaves * GEO::PATCH) * sizeof(float);
-  static unsigned long long attr_set = 0;   // per-device bit mask: the attribute belongs to the device
-  if (mst::first_use_on_device(attr_set)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_kernel<LAYER, SUB>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((conv_kernel<LAYER, SUB>), dim3(grid), dim3(kConvThreads), lds, st, cp);
-  return hipGetLastError();
+  return mst::launch_lds<conv_kernel<LAYER, SUB, MODE>>(dim3(grid), dim3(kConvThreads), ConvGeom<LAYER, SUB>::kLds, st, cp);
 }
 
-hipError_t launch_conv2_rows(const ConvParams& cp, int grid, hipStream_t st) {
-  const size_t lds = (size_t)(2 * ConvGeom<2, 2>::WBP + kConvWaves * RowTiles::PATCH) * sizeof(float);
-  static unsigned long long attr_set = 0;   // per-device bit mask: the attribute belongs to the device
-  if (mst::first_use_on_device(attr_set)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_rows_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(conv2_rows_kernel, dim3(grid), dim3(kConvThreads), lds, st, cp);
-  return hipGetLastError();
+// ---- pieces the eval forward, the training forward and the weight gradients share --------------------------------------
+// sets of `waves` wave tiles per band
+inline int sets_per_band(int B, int tiles_r, int tiles_c, int waves = kConvWaves) { return (B * tiles_r * tiles_c + waves - 1) / waves; }
+
+// What every entry point that takes a described log-mel checks: the layout is one its kernels read (`supported`: the answer of
+// mst_encoder_layout_supported / mst_encoder_train_layout_supported), the float16 layout brings what precision mode `mode`
+// needs (`need_lo`: the low parts, `need_absmax`: stage A's per-clip maximum), channel-minor data is 16-byte aligned.
+int check_logmel_in(const char* who, const mst_logmel_in* lin, bool supported, int mode, bool need_lo, bool need_absmax) {
+  const int lay = lin->layout;
+  MST_REQUIRE(supported, "%s: log-mel layout %d does not fit the kernels of precision mode %d (query mst_encoder_layout_supported / "
+              "mst_encoder_train_layout_supported)", who, lay, mode);
+  MST_REQUIRE(lay != MST_LOGMEL_CM16 || !need_lo || lin->lo, "%s: MST_LOGMEL_CM16 needs the low parts in the split-precision modes", who);
+  MST_REQUIRE(lay != MST_LOGMEL_CM16 || !need_absmax || lin->absmax,
+              "%s: MST_LOGMEL_CM16 needs absmax (stage A's per-clip max |log-mel|) when conv2 runs on float16 too", who);
+  MST_REQUIRE(lay == MST_LOGMEL_REF || ((reinterpret_cast<uintptr_t>(lin->data) | reinterpret_cast<uintptr_t>(lin->lo)) & 15) == 0,
+              "%s: channel-minor log-mel must be 16-byte aligned", who);
+  return MST_OK;
 }
+
+// input planes of conv1 (the log-mel in the reference layout, [B][8][n_mels][frames]) and of conv2 (pool1, [B][nsub][32][H1][W1]),
+// for ConvParams and the weight gradients' parameter structs alike
+template <class P>
+void conv1_input_geometry(P& p, const mst_encoder* e, int frames) {
+  p.in_rows = e->cfg.split_size, p.in_cols = frames;
+  p.in_cstride = e->cfg.n_mels * frames;
+  p.in_bandoff = e->cfg.overlap * frames;
+  p.in_clipstride = (long long)8 * e->cfg.n_mels * frames;
+}
+template <class P>
+void conv2_input_geometry(P& p, const mst_encoder* e, int W1) {
+  p.in_rows = e->H1, p.in_cols = W1;
+  p.in_cstride = e->H1 * W1;
+  p.in_bandoff = 32 * e->H1 * W1;
+  p.in_clipstride = (long long)e->cfg.n_subbands * 32 * e->H1 * W1;
+}
+
+FilmParams film_params(const mst_encoder* e, const float* feats, float* film, float2* aff1, float2* aff2, float* h2, int B) {
+  return FilmParams{feats, e->w0t, e->b0, e->w3t, e->b3, e->hwt, e->hb, e->s1, e->t1, e->s2, e->t2,
+                    film, aff1, aff2, e->cfg.feature_dim, e->cfg.film_hidden, e->cfg.n_subbands, h2, B};
+}
+
+// attention-pooling head: scores, softmax-weighted pooling, projection.  `scored` (or NULL): an event recorded behind the scores
+int launch_head(const mst_encoder* e, const WsLayout& L, char* ws, const float* pool_in, float* emb, int B, hipStream_t st,
+                void* scored = nullptr) {
+  float* scores = reinterpret_cast<float*>(ws + L.scores);
+  AttnParams ap{pool_in, e->att0frag, e->att0_b, e->att2_w, scores, B, e->C, L.W2, e->cfg.attn_hidden};
+  MST_HIP_CHECK(launch_attn_scores(ap, st));
+  if (scored) (void)hipEventRecord(reinterpret_cast<hipEvent_t>(scored), st);
+  float* pooled = reinterpret_cast<float*>(ws + L.pooled);
+  PoolParams pp{pool_in, scores, e->att2_b, pooled, e->C, L.W2, (long long)B * L.W2};
+  const int slices = (e->C + 127) / 128;
+  hipLaunchKernelGGL(attn_pool_kernel, dim3(B, slices), dim3(256), (size_t)((L.W2 + 3) & ~3) * sizeof(float), st, pp);
+  MST_HIP_CHECK(hipGetLastError());
+  ProjParams pj{pooled, e->projfrag, e->proj_b, emb, B, e->C, e->cfg.embed_dim};
+  launch_proj(pj, st);
+  MST_HIP_CHECK(hipGetLastError());
+  return MST_OK;
+}
+
+#ifdef MST_TRACE
+// -DMST_TRACE: a conv kernel writes per-wave cycle counters through ConvParams::yraw; its 10th launch prints them, averaged
+// over the `g` workgroups, per wave index
+struct ConvTrace {
+  float* buf = nullptr;
+  int calls = 0;
+};
+void trace_attach(ConvTrace& t, ConvParams& cp) {
+  if (!t.buf) (void)hipMalloc(&t.buf, 256 * kConvWaves * 8 * sizeof(float));
+  cp.yraw = t.buf;
+}
+void trace_dump(ConvTrace& t, int g, bool conv2) {
+  if (++t.calls != 10) return;
+  (void)hipDeviceSynchronize();
+  std::vector<float> h(256 * kConvWaves * 8);
+  (void)hipMemcpy(h.data(), t.buf, h.size() * sizeof(float), hipMemcpyDeviceToHost);
+  for (int w = 0; w < kConvWaves; ++w) {
+    double a[6] = {0, 0, 0, 0, 0, 0};
+    for (int b = 0; b < g; ++b)
+      for (int i = 0; i < 6; ++i) a[i] += h[(b * kConvWaves + w) * 8 + i] / g;
+    if (conv2)
+      fprintf(stderr, "conv2 trace wave %d: chunks %.1f  staging %.0f (%.0f per chunk)  barrier wait %.0f (%.0f)  taps %.0f (%.0f)  total %.0f\n",
+              w, a[4], a[0], a[0] / a[4], a[1], a[1] / a[4], a[2], a[2] / a[4], a[5]);
+    else
+      fprintf(stderr, "trace wave %d: tiles %.1f  k-steps %.0f (%.0f per tile)  wait for the patch loads %.0f (%.0f)  stage %.0f (%.0f)  barriers %.0f  total %.0f\n",
+              w, a[4], a[0], a[0] / a[4], a[1], a[1] / a[4], a[2], a[2] / a[4], a[3], a[5]);
+  }
+}
+#endif
 
 }  // namespace
 
@@ -3809,7 +3885,7 @@ int mst_encoder_create(mst_encoder** out, const mst_encoder_config* cfg, const m
   MST_REQUIRE((ns - 1) * cfg->overlap + cfg->split_size <= cfg->n_mels, "mst_encoder_create: sub-bands exceed n_mels");
   const int sub = cfg->split_size / 10 > 1 ? cfg->split_size / 10 : 1;
   // first-pool heights 1 and 2 run on the MFMA kernels; larger ones on conv1_generic_kernel, whose LDS holds a whole band's patch
-  MST_REQUIRE(sub <= 2 || (size_t)(392 * 32 + 8 * (cfg->split_size + 6) * kGenPC) * sizeof(float) <= 160 * 1024,
+  MST_REQUIRE(sub <= 2 || conv1_generic_lds(cfg->split_size) <= 160 * 1024,
               "mst_encoder_create: split_size=%d (first-pool height %d) exceeds the generic conv1 kernel's LDS (split_size <= 68)",
               cfg->split_size, sub);
   MST_REQUIRE(cfg->attn_hidden == 256, "mst_encoder_create: attn_hidden must be 256 (got %d)", cfg->attn_hidden);
@@ -4031,13 +4107,9 @@ int mst_encoder_forward_in(const mst_encoder* e, const mst_logmel_in* lin, int f
                            const mst_encoder_taps* taps, void* workspace, size_t workspace_bytes, void* stream) {
   MST_REQUIRE(e && lin && lin->data && feats && emb, "mst_encoder_forward: NULL argument");
   const int lay = lin->layout;
-  MST_REQUIRE(mst_encoder_layout_supported(e, lay),
-              "mst_encoder_forward: log-mel layout %d does not fit this encoder's conv1 kernel (precision mode %d; query "
-              "mst_encoder_layout_supported)", lay, e->conv1_f16x3);
-  MST_REQUIRE(lay != MST_LOGMEL_CM16 || e->conv1_f16x3 == 3 || lin->lo, "mst_encoder_forward: MST_LOGMEL_CM16 needs the low parts in the split-precision modes");
-  MST_REQUIRE(lay != MST_LOGMEL_CM16 || e->conv1_f16x3 < 2 || lin->absmax, "mst_encoder_forward: MST_LOGMEL_CM16 needs absmax (stage A's per-clip max |log-mel|) when conv2 runs on float16 too");
-  MST_REQUIRE(lay == MST_LOGMEL_REF || ((reinterpret_cast<uintptr_t>(lin->data) | reinterpret_cast<uintptr_t>(lin->lo)) & 15) == 0,
-              "mst_encoder_forward: channel-minor log-mel must be 16-byte aligned");
+  if (const int rc = check_logmel_in("mst_encoder_forward", lin, mst_encoder_layout_supported(e, lay), e->conv1_f16x3,
+                                     e->conv1_f16x3 != 3, e->conv1_f16x3 >= 2))
+    return rc;
   const float* logmel = static_cast<const float*>(lin->data);
   MST_REQUIRE(B > 0 && frames >= 20, "mst_encoder_forward: need B>0 and frames>=20 (B=%d frames=%d)", B, frames);
   const WsLayout L = ws_layout(e, B, frames);
@@ -4052,70 +4124,37 @@ int mst_encoder_forward_in(const mst_encoder* e, const mst_logmel_in* lin, int f
   float* pool_in = (taps && taps->pool_in) ? taps->pool_in : reinterpret_cast<float*>(ws + L.pool_in);
   float2* aff1 = reinterpret_cast<float2*>(ws + L.aff1);
   float2* aff2 = reinterpret_cast<float2*>(ws + L.aff2);
-  float* scores = reinterpret_cast<float*>(ws + L.scores);
   auto mark = [&](int i) {
     if (taps && taps->events[i]) (void)hipEventRecord(reinterpret_cast<hipEvent_t>(taps->events[i]), st);
   };
   mark(0);
-  {
-    FilmParams fp{feats, e->w0t, e->b0, e->w3t, e->b3, e->hwt, e->hb, e->s1, e->t1, e->s2, e->t2,
-                  film, aff1, aff2, e->cfg.feature_dim, e->cfg.film_hidden, ns, reinterpret_cast<float*>(ws + L.film_h2), B};
-    MST_HIP_CHECK(launch_film(fp, st));
-  }
+  MST_HIP_CHECK(launch_film(film_params(e, feats, film, aff1, aff2, reinterpret_cast<float*>(ws + L.film_h2), B), st));
   mark(1);
   const int grid = e->num_cus;
+  const dim3 blk(kConvThreads);
   {
     ConvParams cp{};
     cp.in = logmel, cp.wfrag = e->w1frag, cp.aff = aff1, cp.out = pool1, cp.B = B, cp.nsub = ns;
-    cp.in_rows = e->cfg.split_size, cp.in_cols = frames;
-    cp.in_cstride = e->cfg.n_mels * frames;
-    cp.in_bandoff = e->cfg.overlap * frames;
-    cp.in_clipstride = (long long)8 * e->cfg.n_mels * frames;
+    conv1_input_geometry(cp, e, frames);
     cp.in_lo = lin->lo, cp.cm_mels = e->cfg.n_mels, cp.cm_overlap = e->cfg.overlap;
     cp.out_rows = e->H1, cp.out_cols = L.W1;
     cp.tiles_r = e->H1;
     cp.tiles_c = e->sub == 2 ? (L.W1 + 7) / 8 : (L.W1 + 15) / 16;
-    cp.sets_per_band = (B * cp.tiles_r * cp.tiles_c + kConvWaves - 1) / kConvWaves;
+    // fp32 on 2 x 40 tiles: the band-resident kernel; 16-mel sub-bands (pool height 1) take it with two 1 x 5 windows per lane
+    const bool resident = e->sub <= 2 && !e->conv1_f16x3 && conv1_resident_geometry(e);
+    if (e->sub == 1 && (e->conv1_f16x3 || resident)) {   // 16-mel sub-bands: pool height 1 on the 2 x 40 tiles
+      cp.pool_h = 1;
+      cp.tiles_r = e->cfg.split_size / 2;
+      cp.tiles_c = (L.W1 + 7) / 8;
+    }
+    cp.sets_per_band = sets_per_band(B, cp.tiles_r, cp.tiles_c);
     const int g = std::min(grid, ns * cp.sets_per_band);
     hipError_t err;
     if (e->sub > 2) {   // first-pool heights >= 3: the generic kernel (reference layout, exact fp32)
       MST_REQUIRE(lay == MST_LOGMEL_REF && e->conv1_f16x3 == 0, "mst_encoder_forward: split_size=%d runs in the reference layout, fp32 only", e->cfg.split_size);
-      const size_t lds = (size_t)(392 * 32 + 8 * (e->cfg.split_size + 6) * kGenPC) * sizeof(float);
-      static unsigned long long attr_gen = 0;   // per-device bit mask: the attribute belongs to the device
-      if (mst::first_use_on_device(attr_gen)) {
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_generic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (err != hipSuccess) return mst::fail(MST_EHIP, "conv1 generic attribute failed: %s", hipGetErrorString(err));
-      }
-      hipLaunchKernelGGL(conv1_generic_kernel, dim3((L.W1 + kGenCols - 1) / kGenCols, B * ns), dim3(256), lds, st, cp, e->sub);
-      err = hipGetLastError();
+      err = mst::launch_lds<conv1_generic_kernel>(dim3((L.W1 + kGenCols - 1) / kGenCols, B * ns), dim3(256),
+                                                  conv1_generic_lds(e->cfg.split_size), st, cp, e->sub);
     } else if (e->conv1_f16x3) {   // (set_precision admits the f16 modes only for geometries that fit the 2 x 40 tiles)
-      using C = CC<1, 2>;
-      if (e->sub == 1) {   // 16-mel sub-bands: pool height 1 on the same tiles
-        cp.pool_h = 1;
-        cp.tiles_r = e->cfg.split_size / 2;
-        cp.tiles_c = (L.W1 + 7) / 8;
-        cp.sets_per_band = (B * cp.tiles_r * cp.tiles_c + kConvWaves - 1) / kConvWaves;
-      }
-      const int g = std::min(grid, ns * cp.sets_per_band);
-      constexpr size_t lds = (size_t)(kF16Steps * C::NT * 2 * 64 + kConvWaves * 2 * C::PR * C::PC) * 16;
-      constexpr size_t lds_e3 = (size_t)(kF16StepsE * C::NT * 2 * 64 + kConvWaves * 2 * kF16ePatch) * 16;   // conv1_f16e_kernel
-      constexpr size_t lds_e1 = (size_t)(kF16StepsE * C::NT * 64 + kF16eWaves<1> * kF16ePatch) * 16;
-      static_assert(lds_e3 <= 160 * 1024, "conv1_f16e_kernel<3> must fit one CU's LDS");
-      static unsigned long long attr16 = 0;   // per-device bit mask: the attribute belongs to the device
-      if (mst::first_use_on_device(attr16)) {
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_f16x3_kernel<2, 3>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err == hipSuccess)
-          err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_f16x3_kernel<2, 1>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err == hipSuccess)
-          err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_f16e_kernel<3>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_e3);
-        if (err == hipSuccess)
-          err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_f16e_kernel<1>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_e1);
-        if (err != hipSuccess) return mst::fail(MST_EHIP, "conv1 f16x3 attribute failed: %s", hipGetErrorString(err));
-      }
       const bool both = e->conv1_f16x3 >= 2;
       cp.f16_winv = e->f16_winv1;
       if (both && !(taps && taps->pool1)) cp.out = nullptr;   // fp32 pool1 only when a tap asks for it
@@ -4138,64 +4177,29 @@ int mst_encoder_forward_in(const mst_encoder* e, const mst_logmel_in* lin, int f
       if (lay == MST_LOGMEL_CM16) {   // the bank-conflict-free build (its own k order: w1frag16e)
         const h16x8* wfe = reinterpret_cast<const h16x8*>(e->w1frag16e);
         if (e->conv1_f16x3 == 3) {   // plain f16: 12 waves per workgroup, sets of 12 tiles
-          cp.sets_per_band = (B * cp.tiles_r * cp.tiles_c + kF16eWaves<1> - 1) / kF16eWaves<1>;
+          cp.sets_per_band = sets_per_band(B, cp.tiles_r, cp.tiles_c, kF16eWaves<1>);
           const int g1 = std::min(grid, ns * cp.sets_per_band);
-          hipLaunchKernelGGL((conv1_f16e_kernel<1>), dim3(g1), dim3(kF16eWaves<1> * 64), lds_e1, st, cp, wfe, oh, ol);
+          err = mst::launch_lds<conv1_f16e_kernel<1>>(dim3(g1), dim3(kF16eWaves<1> * 64), kConv1F16eLds<1>, st, cp, wfe, oh, ol);
         }
-        else hipLaunchKernelGGL((conv1_f16e_kernel<3>), dim3(g), dim3(kConvThreads), lds_e3, st, cp, wfe, oh, ol);
-      } else if (e->conv1_f16x3 == 3) hipLaunchKernelGGL((conv1_f16x3_kernel<2, 1>), dim3(g), dim3(kConvThreads), lds, st, cp, wf, oh, ol);
-      else hipLaunchKernelGGL((conv1_f16x3_kernel<2, 3>), dim3(g), dim3(kConvThreads), lds, st, cp, wf, oh, ol);
-      err = hipGetLastError();
-    } else if (conv1_resident_geometry(e)) {
-      // band-resident kernel on 2 x 40 tiles; 16-mel sub-bands (pool height 1) take it with two 1 x 5 windows per lane
-      using C = CC<1, 2>;
-      if (e->sub == 1) {
-        cp.pool_h = 1;
-        cp.tiles_r = e->cfg.split_size / 2;
-        cp.tiles_c = (L.W1 + 7) / 8;
-        cp.sets_per_band = (B * cp.tiles_r * cp.tiles_c + kConvWaves - 1) / kConvWaves;
-      }
+        else err = mst::launch_lds<conv1_f16e_kernel<3>>(dim3(g), blk, kConv1F16eLds<3>, st, cp, wfe, oh, ol);
+      } else if (e->conv1_f16x3 == 3) err = mst::launch_lds<conv1_f16x3_kernel<2, 1>>(dim3(g), blk, kConv1F16Lds<2>, st, cp, wf, oh, ol);
+      else err = mst::launch_lds<conv1_f16x3_kernel<2, 3>>(dim3(g), blk, kConv1F16Lds<2>, st, cp, wf, oh, ol);
+    } else if (resident) {
       if (!getenv("MST_CONV1_BAND_MAJOR")) {   // eval forward: the bands of a clip group next to each other (decode() of the kernel)
         const char* env = getenv("MST_CONV1_CLIP_GROUP");
         cp.clip_major = std::max(1, std::min(B, env ? atoi(env) : 1));   // 1: every (clip, band) patch comes from HBM exactly once (measured)
-        cp.sets_per_band = (cp.clip_major * cp.tiles_r * cp.tiles_c + kConvWaves - 1) / kConvWaves;
+        cp.sets_per_band = sets_per_band(cp.clip_major, cp.tiles_r, cp.tiles_c);
       }
       const int g = std::min(grid, (cp.clip_major ? (B + cp.clip_major - 1) / cp.clip_major : 1) * ns * cp.sets_per_band);
-      constexpr size_t lds = (size_t)(2 * 49 * C::NT * 64 + kConvWaves * 8 * C::PR * C::PC) * sizeof(float);
-      static unsigned long long attr_set = 0;   // per-device bit mask: the attribute belongs to the device
-      if (mst::first_use_on_device(attr_set)) {
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_resident_kernel<2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err == hipSuccess)
-          err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_resident_kernel<2, 0, 1>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err != hipSuccess) return mst::fail(MST_EHIP, "conv1 attribute failed: %s", hipGetErrorString(err));
-      }
 #ifdef MST_TRACE
-      static float* trace_buf = nullptr;
-      if (!trace_buf) (void)hipMalloc(&trace_buf, 256 * kConvWaves * 8 * sizeof(float));
-      cp.yraw = trace_buf;
+      static ConvTrace trace;
+      trace_attach(trace, cp);
 #endif
-      if (lay == MST_LOGMEL_CM32) hipLaunchKernelGGL((conv1_resident_kernel<2, 0, 1>), dim3(g), dim3(kConvThreads), lds, st, cp);
-      else hipLaunchKernelGGL((conv1_resident_kernel<2>), dim3(g), dim3(kConvThreads), lds, st, cp);
+      if (lay == MST_LOGMEL_CM32) err = mst::launch_lds<conv1_resident_kernel<2, 0, 1>>(dim3(g), blk, kConv1ResidentLds<2>, st, cp);
+      else err = mst::launch_lds<conv1_resident_kernel<2>>(dim3(g), blk, kConv1ResidentLds<2>, st, cp);
 #ifdef MST_TRACE
-      {
-        static int calls = 0;
-        if (++calls == 10) {
-          (void)hipDeviceSynchronize();
-          std::vector<float> h(256 * kConvWaves * 8);
-          (void)hipMemcpy(h.data(), trace_buf, h.size() * sizeof(float), hipMemcpyDeviceToHost);
-          for (int w = 0; w < kConvWaves; ++w) {   // average over the workgroups, per wave index
-            double a[6] = {0, 0, 0, 0, 0, 0};
-            for (int b = 0; b < g; ++b)
-              for (int i = 0; i < 6; ++i) a[i] += h[(b * kConvWaves + w) * 8 + i] / g;
-            fprintf(stderr, "trace wave %d: tiles %.1f  k-steps %.0f (%.0f per tile)  wait for the patch loads %.0f (%.0f)  stage %.0f (%.0f)  barriers %.0f  total %.0f\n",
-                    w, a[4], a[0], a[0] / a[4], a[1], a[1] / a[4], a[2], a[2] / a[4], a[3], a[5]);
-          }
-        }
-      }
+      trace_dump(trace, g, false);
 #endif
-      err = hipGetLastError();
     } else {
       err = e->sub == 2 ? launch_conv<1, 2>(cp, g, st) : launch_conv<1, 1>(cp, g, st);
     }
@@ -4205,40 +4209,25 @@ int mst_encoder_forward_in(const mst_encoder* e, const mst_logmel_in* lin, int f
   {
     ConvParams cp{};
     cp.in = pool1, cp.wfrag = e->w2frag, cp.aff = aff2, cp.out = pool_in, cp.B = B, cp.nsub = ns;
-    cp.in_rows = e->H1, cp.in_cols = L.W1;
-    cp.in_cstride = e->H1 * L.W1;
-    cp.in_bandoff = 32 * e->H1 * L.W1;
-    cp.in_clipstride = (long long)ns * 32 * e->H1 * L.W1;
+    conv2_input_geometry(cp, e, L.W1);
     cp.out_rows = e->FD, cp.out_cols = L.W2;
     cp.tiles_r = (e->FD + 1) / 2;
     cp.tiles_c = (L.W2 + 1) / 2;
-    cp.sets_per_band = (B * cp.tiles_r * cp.tiles_c + kConvWaves - 1) / kConvWaves;
+    cp.sets_per_band = sets_per_band(B, cp.tiles_r, cp.tiles_c);
     const int g = std::min(grid, ns * cp.sets_per_band);
     hipError_t err;
     if (e->conv1_f16x3 >= 2) {
-      constexpr size_t lds = (size_t)(kF16Steps * 4 * 2 * 64 + kConvWaves * 2 * 14 * 14) * 16;
-      static unsigned long long attr = 0;   // per-device bit mask: the attribute belongs to the device
-      if (mst::first_use_on_device(attr)) {
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_f16x3_kernel<3>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err == hipSuccess)
-          err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_f16x3_kernel<1>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err != hipSuccess) return mst::fail(MST_EHIP, "conv2 f16x3 attribute failed: %s", hipGetErrorString(err));
-      }
       cp.f16_scale = reinterpret_cast<const float*>(ws + L.f16scale);
       cp.f16_winv = e->f16_winv2;
       const h16x8* ih = reinterpret_cast<const h16x8*>(ws + L.pool1_h16);
       const h16x8* il = reinterpret_cast<const h16x8*>(ws + L.pool1_l16);
       const h16x8* wf = reinterpret_cast<const h16x8*>(e->w2frag16);
-      if (e->conv1_f16x3 == 3) hipLaunchKernelGGL((conv2_f16x3_kernel<1>), dim3(g), dim3(kConvThreads), lds, st, cp, ih, il, wf);
-      else hipLaunchKernelGGL((conv2_f16x3_kernel<3>), dim3(g), dim3(kConvThreads), lds, st, cp, ih, il, wf);
-      err = hipGetLastError();
+      if (e->conv1_f16x3 == 3) err = mst::launch_lds<conv2_f16x3_kernel<1>>(dim3(g), blk, kConv2F16Lds, st, cp, ih, il, wf);
+      else err = mst::launch_lds<conv2_f16x3_kernel<3>>(dim3(g), blk, kConv2F16Lds, st, cp, ih, il, wf);
     } else {
 #ifdef MST_TRACE
-      static float* trace_buf2 = nullptr;
-      if (!trace_buf2) (void)hipMalloc(&trace_buf2, 256 * kConvWaves * 8 * sizeof(float));
-      cp.yraw = trace_buf2;
+      static ConvTrace trace;
+      trace_attach(trace, cp);
 #endif
       // 10-row planes (FD == 2: the 20-mel sub-bands): row-pure 4 x 16 tiles (conv2_rows_kernel); MST_CONV2_TILES=8x8, read
       // per launch, keeps conv_kernel's 8 x 8 tiles there too (same bits: the yardstick of tests/test_conv2_row_tiles_gpu.py,
@@ -4251,46 +4240,18 @@ int mst_encoder_forward_in(const mst_encoder* e, const mst_logmel_in* lin, int f
         cp.rt_fold = rem == 1 || rem == 2;
         cp.rt_pair_sets = (B * cp.rt_blocks + 3) / 4;
         cp.sets_per_band = cp.rt_pair_sets + (B * cp.rt_fold + kConvWaves - 1) / kConvWaves;
-        err = launch_conv2_rows(cp, std::min(grid, ns * cp.sets_per_band), st);
+        err = mst::launch_lds<conv2_rows_kernel>(dim3(std::min(grid, ns * cp.sets_per_band)), blk, RowTiles::kLds, st, cp);
       } else {
         err = launch_conv<2, 2>(cp, g, st);
       }
 #ifdef MST_TRACE
-      {
-        static int calls = 0;
-        if (++calls == 10) {
-          (void)hipDeviceSynchronize();
-          std::vector<float> h(256 * kConvWaves * 8);
-          (void)hipMemcpy(h.data(), trace_buf2, h.size() * sizeof(float), hipMemcpyDeviceToHost);
-          for (int w = 0; w < kConvWaves; ++w) {
-            double a[6] = {0, 0, 0, 0, 0, 0};
-            for (int b = 0; b < g; ++b)
-              for (int i = 0; i < 6; ++i) a[i] += h[(b * kConvWaves + w) * 8 + i] / g;
-            fprintf(stderr, "conv2 trace wave %d: chunks %.1f  staging %.0f (%.0f per chunk)  barrier wait %.0f (%.0f)  taps %.0f (%.0f)  total %.0f\n",
-                    w, a[4], a[0], a[0] / a[4], a[1], a[1] / a[4], a[2], a[2] / a[4], a[5]);
-          }
-        }
-      }
+      trace_dump(trace, g, true);
 #endif
     }
     if (err != hipSuccess) return mst::fail(MST_EHIP, "conv2 launch failed: %s", hipGetErrorString(err));
   }
   mark(3);
-  {
-    AttnParams ap{pool_in, e->att0frag, e->att0_b, e->att2_w, scores, B, e->C, L.W2, e->cfg.attn_hidden};
-    MST_HIP_CHECK(launch_attn_scores(ap, st));
-  }
-  mark(4);
-  {
-    float* pooled = reinterpret_cast<float*>(ws + L.pooled);
-    PoolParams pp{pool_in, scores, e->att2_b, pooled, e->C, L.W2, (long long)B * L.W2};
-    const int slices = (e->C + 127) / 128;
-    hipLaunchKernelGGL(attn_pool_kernel, dim3(B, slices), dim3(256), (size_t)((L.W2 + 3) & ~3) * sizeof(float), st, pp);
-    MST_HIP_CHECK(hipGetLastError());
-    ProjParams pj{pooled, e->projfrag, e->proj_b, emb, B, e->C, e->cfg.embed_dim};
-    launch_proj(pj, st);
-    MST_HIP_CHECK(hipGetLastError());
-  }
+  if (const int rc = launch_head(e, L, ws, pool_in, emb, B, st, taps ? taps->events[4] : nullptr)) return rc;
   mark(5);
   return MST_OK;
 }
@@ -4387,12 +4348,9 @@ int mst_encoder_forward_train_in(const mst_encoder* e, const mst_logmel_in* lin,
   MST_REQUIRE(e && e->sub <= 2, "mst_encoder_forward_train: the training kernels cover first-pool heights 1 and 2 (split_size < 30)");
   MST_REQUIRE(e && lin && lin->data && (feats || (taps && taps->film_in)), "mst_encoder_forward_train: NULL argument");
   const int lay = lin->layout;
-  MST_REQUIRE(mst_encoder_train_layout_supported(e, lay),
-              "mst_encoder_forward_train: log-mel layout %d does not fit the training kernels of precision mode %d (query "
-              "mst_encoder_train_layout_supported)", lay, e->train_f16);
-  MST_REQUIRE(lay != MST_LOGMEL_CM16 || e->train_f16 == 1 || lin->lo, "mst_encoder_forward_train: MST_LOGMEL_CM16 needs the low parts in the split-precision mode");
-  MST_REQUIRE(lay == MST_LOGMEL_REF || ((reinterpret_cast<uintptr_t>(lin->data) | reinterpret_cast<uintptr_t>(lin->lo)) & 15) == 0,
-              "mst_encoder_forward_train: channel-minor log-mel must be 16-byte aligned");
+  if (const int rc = check_logmel_in("mst_encoder_forward_train", lin, mst_encoder_train_layout_supported(e, lay), e->train_f16,
+                                     e->train_f16 != 1, false))
+    return rc;
   const float* logmel = static_cast<const float*>(lin->data);
   MST_REQUIRE(B > 0 && frames >= 20, "mst_encoder_forward_train: need B>0 and frames>=20 (B=%d frames=%d)", B, frames);
   const TrainLayout T = train_layout(e, B, frames);
@@ -4408,7 +4366,6 @@ int mst_encoder_forward_train_in(const mst_encoder* e, const mst_logmel_in* lin,
   float* pool_in = (taps && taps->pool_in) ? taps->pool_in : reinterpret_cast<float*>(ws + L.pool_in);
   float2* aff1 = reinterpret_cast<float2*>(ws + L.aff1);
   float2* aff2 = reinterpret_cast<float2*>(ws + L.aff2);
-  float* scores = reinterpret_cast<float*>(ws + L.scores);
   float* y1 = reinterpret_cast<float*>(ws + T.y1);
   float* y2 = reinterpret_cast<float*>(ws + T.y2);
   mst::DetAcc* stats1 = reinterpret_cast<mst::DetAcc*>(ws + T.stats1);
@@ -4421,7 +4378,7 @@ int mst_encoder_forward_train_in(const mst_encoder* e, const mst_logmel_in* lin,
   const bool run_a = phase == 0 || phase == 1, run_b = phase == 0 || phase == 2, run_c = phase == 0 || phase == 3;
   const double cscale = (taps && taps->count_scale > 0.0) ? taps->count_scale : 1.0;
   const int grid = e->num_cus;
-  hipError_t err;
+  const dim3 blk(kConvThreads);
   if (run_a) {
   // (stats1 and stats2 are neighbours in the workspace: one fill)
   MST_HIP_CHECK(hipMemsetAsync(stats1, 0, (T.stats2 - T.stats1) + (size_t)ns * 64 * 2 * sizeof(mst::DetAcc), st));
@@ -4431,25 +4388,19 @@ int mst_encoder_forward_train_in(const mst_encoder* e, const mst_logmel_in* lin,
   if (taps && taps->film_in) {   // FiLM parameters computed by the caller (its MLP keeps its autograd graph)
     MST_HIP_CHECK(hipMemcpyAsync(film, taps->film_in, (size_t)B * ns * 192 * 4, hipMemcpyDeviceToDevice, st));
   } else {   // FiLM MLP (its eval-mode affines are overwritten by bn_fold_kernel below)
-    FilmParams fp{feats, e->w0t, e->b0, e->w3t, e->b3, e->hwt, e->hb, e->s1, e->t1, e->s2, e->t2,
-                  film, aff1, aff2, e->cfg.feature_dim, e->cfg.film_hidden, ns, reinterpret_cast<float*>(ws + L.film_h2), B};
-    MST_HIP_CHECK(launch_film(fp, st));
+    MST_HIP_CHECK(launch_film(film_params(e, feats, film, aff1, aff2, reinterpret_cast<float*>(ws + L.film_h2), B), st));
   }
   {   // conv1 raw + statistics
     ConvParams cp{};
     cp.in = logmel, cp.wfrag = e->w1frag, cp.B = B, cp.nsub = ns;
-    cp.in_rows = e->cfg.split_size, cp.in_cols = frames;
-    cp.in_cstride = e->cfg.n_mels * frames;
-    cp.in_bandoff = e->cfg.overlap * frames;
-    cp.in_clipstride = (long long)8 * e->cfg.n_mels * frames;
+    conv1_input_geometry(cp, e, frames);
     cp.out_rows = e->H1, cp.out_cols = L.W1;
     cp.tiles_r = T.tr1, cp.tiles_c = T.tc1;
-    cp.sets_per_band = (B * cp.tiles_r * cp.tiles_c + kConvWaves - 1) / kConvWaves;
+    cp.sets_per_band = sets_per_band(B, cp.tiles_r, cp.tiles_c);
     cp.yraw = y1, cp.stats = stats1, cp.bias = e->c1b, cp.raw_rows = e->cfg.split_size, cp.raw_cols = frames;
     cp.acc_tr = T.tr1, cp.acc_tc = T.tc1;
     const int g = std::min(grid, ns * cp.sets_per_band);
     if (train_fwd16(e)) {   // f16 operands (mode 1) or 3-term split precision (mode 2), fp32 accumulate (encoder_f16train.inc)
-      using C = CC<1, 2>;
       unsigned* xmax = reinterpret_cast<unsigned*>(ws + T.t_xmax);   // max |log-mel| per clip: bounds for the range scales
       if (lin->absmax) {   // stage A found it while it wrote the log-mel
         MST_HIP_CHECK(hipMemcpyAsync(xmax, lin->absmax, (size_t)B * sizeof(unsigned), hipMemcpyDeviceToDevice, st));
@@ -4464,52 +4415,20 @@ int mst_encoder_forward_train_in(const mst_encoder* e, const mst_logmel_in* lin,
         hipLaunchKernelGGL(f16_yscale_kernel, dim3(ns), dim3(64), 0, st, e->w1norm, e->c1b, 32, xmax, B, static_cast<const float*>(nullptr), ys1);
         cp.yraw16 = reinterpret_cast<_Float16*>(y1), cp.y_scale = ys1;
       }
-      constexpr size_t lds = (size_t)(kF16Steps * C::NT * 2 * 64 + kConvWaves * 2 * C::PR * C::PC) * 16;
-      static unsigned long long attr_set = 0;   // per-device bit mask: the attribute belongs to the device
-      if (mst::first_use_on_device(attr_set)) {
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_f16x3_kernel<2, 1, 2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err == hipSuccess)
-          err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_f16x3_kernel<2, 3, 1>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err == hipSuccess)
-          err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_f16x3_kernel<2, 1, 2, 2>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err == hipSuccess)
-          err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_f16x3_kernel<2, 3, 1, 2>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err != hipSuccess) return mst::fail(MST_EHIP, "conv1 (f16 train) attribute failed: %s", hipGetErrorString(err));
-      }
       cp.f16_winv = e->f16_winv1;
       const h16x8* wf = reinterpret_cast<const h16x8*>(e->w1frag16);
       _Float16* none = nullptr;
+      constexpr size_t lds = kConv1F16Lds<2>;
       if (lay == MST_LOGMEL_CM16) {   // ready-made float16 operands: 16-byte copies instead of the fp32 -> f16 staging
-        if (e->train_f16 == 2) hipLaunchKernelGGL((conv1_f16x3_kernel<2, 3, 1, 2>), dim3(g), dim3(kConvThreads), lds, st, cp, wf, none, none);
-        else hipLaunchKernelGGL((conv1_f16x3_kernel<2, 1, 2, 2>), dim3(g), dim3(kConvThreads), lds, st, cp, wf, none, none);
-      } else if (e->train_f16 == 2) hipLaunchKernelGGL((conv1_f16x3_kernel<2, 3, 1>), dim3(g), dim3(kConvThreads), lds, st, cp, wf, none, none);
-      else hipLaunchKernelGGL((conv1_f16x3_kernel<2, 1, 2>), dim3(g), dim3(kConvThreads), lds, st, cp, wf, none, none);
+        if (e->train_f16 == 2) MST_HIP_CHECK(mst::launch_lds<conv1_f16x3_kernel<2, 3, 1, 2>>(dim3(g), blk, lds, st, cp, wf, none, none));
+        else MST_HIP_CHECK(mst::launch_lds<conv1_f16x3_kernel<2, 1, 2, 2>>(dim3(g), blk, lds, st, cp, wf, none, none));
+      } else if (e->train_f16 == 2) MST_HIP_CHECK(mst::launch_lds<conv1_f16x3_kernel<2, 3, 1>>(dim3(g), blk, lds, st, cp, wf, none, none));
+      else MST_HIP_CHECK(mst::launch_lds<conv1_f16x3_kernel<2, 1, 2>>(dim3(g), blk, lds, st, cp, wf, none, none));
     } else if (e->sub == 2) {
-      using C = CC<1, 2>;
-      constexpr size_t lds = (size_t)(2 * 49 * C::NT * 64 + kConvWaves * 8 * C::PR * C::PC) * sizeof(float);
-      static unsigned long long attr_set = 0;   // per-device bit mask: the attribute belongs to the device
-      if (mst::first_use_on_device(attr_set)) {
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_resident_kernel<2, 1>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err != hipSuccess) return mst::fail(MST_EHIP, "conv1 (train) attribute failed: %s", hipGetErrorString(err));
-      }
-      hipLaunchKernelGGL((conv1_resident_kernel<2, 1>), dim3(g), dim3(kConvThreads), lds, st, cp);
+      MST_HIP_CHECK(mst::launch_lds<conv1_resident_kernel<2, 1>>(dim3(g), blk, kConv1ResidentLds<2>, st, cp));
     } else {   // 10..19-mel sub-bands (pool height 1): the chunked kernel with the raw epilogue
-      using GEO = ConvGeom<1, 1>;
-      const size_t lds = (size_t)(2 * GEO::WBP + kConvWaves * GEO::PATCH) * sizeof(float);
-      static unsigned long long attr_set = 0;   // per-device bit mask: the attribute belongs to the device
-      if (mst::first_use_on_device(attr_set)) {
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_kernel<1, 1, 1>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err != hipSuccess) return mst::fail(MST_EHIP, "conv1 (train) attribute failed: %s", hipGetErrorString(err));
-      }
-      hipLaunchKernelGGL((conv_kernel<1, 1, 1>), dim3(g), dim3(kConvThreads), lds, st, cp);
+      MST_HIP_CHECK(launch_conv<1, 1, 1>(cp, g, st));
     }
-    MST_HIP_CHECK(hipGetLastError());
   }
   }   // run_a
   if (run_b) {
@@ -4546,33 +4465,20 @@ int mst_encoder_forward_train_in(const mst_encoder* e, const mst_logmel_in* lin,
   {   // conv2 raw + statistics (all 10 rows: rows 8, 9 never reach MaxPool(4,4) but count in the batch statistics)
     ConvParams cp{};
     cp.in = pool1, cp.wfrag = e->w2frag, cp.B = B, cp.nsub = ns;
-    cp.in_rows = e->H1, cp.in_cols = L.W1;
-    cp.in_cstride = e->H1 * L.W1;
-    cp.in_bandoff = 32 * e->H1 * L.W1;
-    cp.in_clipstride = (long long)ns * 32 * e->H1 * L.W1;
+    conv2_input_geometry(cp, e, L.W1);
     cp.out_rows = e->FD, cp.out_cols = L.W2;
     // the last tile row holds at most 2 real output rows (rows 8, 9 of 10 at the default geometry): those go through
     // the 2 x 40-tile strip kernel instead of 8 x 8 tiles that would be 75 % padding
     const int rows_last = e->H1 - 8 * (T.tr2 - 1);
     const bool strip = T.tr2 >= 2 && rows_last <= 2 && !getenv("MST_CONV2_NO_STRIP");
     cp.tiles_r = strip ? T.tr2 - 1 : T.tr2, cp.tiles_c = T.tc2;
-    cp.sets_per_band = (B * cp.tiles_r * cp.tiles_c + kConvWaves - 1) / kConvWaves;
+    cp.sets_per_band = sets_per_band(B, cp.tiles_r, cp.tiles_c);
     cp.yraw = y2, cp.stats = stats2, cp.bias = e->c2b, cp.raw_rows = e->H1, cp.raw_cols = L.W1;
     cp.acc_tr = T.tr2, cp.acc_tc = T.tc2;
     if (train_fwd16(e)) {   // all tile rows on the f16 kernel (no strip: its padding costs less than a second launch)
       cp.tiles_r = T.tr2;
-      cp.sets_per_band = (B * cp.tiles_r * cp.tiles_c + kConvWaves - 1) / kConvWaves;
+      cp.sets_per_band = sets_per_band(B, cp.tiles_r, cp.tiles_c);
       const int g = std::min(grid, ns * cp.sets_per_band);
-      constexpr size_t lds = (size_t)(kF16Steps * 4 * 2 * 64 + kConvWaves * 2 * 14 * 14) * 16;
-      static unsigned long long attr_set = 0;   // per-device bit mask: the attribute belongs to the device
-      if (mst::first_use_on_device(attr_set)) {
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_f16x3_kernel<1, 2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err == hipSuccess)
-          err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_f16x3_kernel<3, 1>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err != hipSuccess) return mst::fail(MST_EHIP, "conv2 (f16 train) attribute failed: %s", hipGetErrorString(err));
-      }
       cp.f16_scale = reinterpret_cast<const float*>(ws + T.t_f16scale);
       cp.f16_winv = e->f16_winv2;
       if (e->train_f16 == 1) {
@@ -4584,40 +4490,19 @@ int mst_encoder_forward_train_in(const mst_encoder* e, const mst_logmel_in* lin,
       const h16x8* ih = reinterpret_cast<const h16x8*>(ws + T.t_pool1_h16);
       const h16x8* wf2 = reinterpret_cast<const h16x8*>(e->w2frag16);
       if (e->train_f16 == 2)
-        hipLaunchKernelGGL((conv2_f16x3_kernel<3, 1>), dim3(g), dim3(kConvThreads), lds, st, cp, ih,
-                           reinterpret_cast<const h16x8*>(ws + T.t_pool1_l16), wf2);
-      else hipLaunchKernelGGL((conv2_f16x3_kernel<1, 2>), dim3(g), dim3(kConvThreads), lds, st, cp, ih, ih, wf2);
-      MST_HIP_CHECK(hipGetLastError());
+        MST_HIP_CHECK(mst::launch_lds<conv2_f16x3_kernel<3, 1>>(dim3(g), blk, kConv2F16Lds, st, cp, ih,
+                                                                 reinterpret_cast<const h16x8*>(ws + T.t_pool1_l16), wf2));
+      else MST_HIP_CHECK(mst::launch_lds<conv2_f16x3_kernel<1, 2>>(dim3(g), blk, kConv2F16Lds, st, cp, ih, ih, wf2));
     } else {
-      const int g = std::min(grid, ns * cp.sets_per_band);
-      using GEO = ConvGeom<2, 2>;
-      const size_t lds = (size_t)(2 * GEO::WBP + kConvWaves * GEO::PATCH) * sizeof(float);
-      static unsigned long long attr_set = 0;   // per-device bit mask: the attribute belongs to the device
-      if (mst::first_use_on_device(attr_set)) {
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_kernel<2, 2, 1>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err != hipSuccess) return mst::fail(MST_EHIP, "conv2 (train) attribute failed: %s", hipGetErrorString(err));
-      }
-      hipLaunchKernelGGL((conv_kernel<2, 2, 1>), dim3(g), dim3(kConvThreads), lds, st, cp);
-      MST_HIP_CHECK(hipGetLastError());
+      MST_HIP_CHECK(launch_conv<2, 2, 1>(cp, std::min(grid, ns * cp.sets_per_band), st));
     }
     if (strip && !train_fwd16(e)) {
       ConvParams sp = cp;
       sp.row_off = 8 * (T.tr2 - 1);
       sp.tiles_r = (rows_last + 1) / 2, sp.tiles_c = (L.W1 + 39) / 40;
-      sp.sets_per_band = (B * sp.tiles_r * sp.tiles_c + kConvWaves - 1) / kConvWaves;
-      const int g = std::min(grid, ns * sp.sets_per_band);
-      using GEO = ConvGeom<4, 2>;
-      static_assert(GEO::WBP == ConvGeom<2, 2>::WBP, "the strip kernel streams conv2's forward weight fragments");
-      const size_t lds = (size_t)(2 * GEO::WBP + kConvWaves * GEO::PATCH) * sizeof(float);
-      static unsigned long long attr_set = 0;   // per-device bit mask: the attribute belongs to the device
-      if (mst::first_use_on_device(attr_set)) {
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_kernel<4, 2, 3>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err != hipSuccess) return mst::fail(MST_EHIP, "conv2 strip attribute failed: %s", hipGetErrorString(err));
-      }
-      hipLaunchKernelGGL((conv_kernel<4, 2, 3>), dim3(g), dim3(kConvThreads), lds, st, sp);
-      MST_HIP_CHECK(hipGetLastError());
+      sp.sets_per_band = sets_per_band(B, sp.tiles_r, sp.tiles_c);
+      static_assert(ConvGeom<4, 2>::WBP == ConvGeom<2, 2>::WBP, "the strip kernel streams conv2's forward weight fragments");
+      MST_HIP_CHECK(launch_conv<4, 2, 3>(sp, std::min(grid, ns * sp.sets_per_band), st));
     }
   }
   }   // run_b
@@ -4634,16 +4519,7 @@ int mst_encoder_forward_train_in(const mst_encoder* e, const mst_logmel_in* lin,
     MST_HIP_CHECK(hipGetLastError());
   }
   if (emb) {   // attention pooling head (emb == NULL: the caller runs its own head on pool_in)
-    AttnParams ap{pool_in, e->att0frag, e->att0_b, e->att2_w, scores, B, e->C, L.W2, e->cfg.attn_hidden};
-    MST_HIP_CHECK(launch_attn_scores(ap, st));
-    float* pooled = reinterpret_cast<float*>(ws + L.pooled);
-    PoolParams pp{pool_in, scores, e->att2_b, pooled, e->C, L.W2, (long long)B * L.W2};
-    const int slices = (e->C + 127) / 128;
-    hipLaunchKernelGGL(attn_pool_kernel, dim3(B, slices), dim3(256), (size_t)((L.W2 + 3) & ~3) * sizeof(float), st, pp);
-    MST_HIP_CHECK(hipGetLastError());
-    ProjParams pj{pooled, e->projfrag, e->proj_b, emb, B, e->C, e->cfg.embed_dim};
-    launch_proj(pj, st);
-    MST_HIP_CHECK(hipGetLastError());
+    if (const int rc = launch_head(e, L, ws, pool_in, emb, B, st)) return rc;
   }
   if (taps && taps->film) MST_HIP_CHECK(hipMemcpyAsync(taps->film, film, (size_t)B * ns * 192 * 4, hipMemcpyDeviceToDevice, st));
   if (taps && taps->bn1) MST_HIP_CHECK(hipMemcpyAsync(taps->bn1, ws + T.bn1, (size_t)ns * 32 * 8, hipMemcpyDeviceToDevice, st));
@@ -4974,11 +4850,9 @@ int mst_encoder_train_conv1_wgrad_in(const mst_encoder* e, const mst_logmel_in* 
                                      void* workspace, size_t workspace_bytes, void* stream) {
   MST_REQUIRE(e && lin && lin->data && dw, "mst_encoder_train_conv1_wgrad: NULL argument");
   const int lay = lin->layout;
-  MST_REQUIRE(mst_encoder_train_layout_supported(e, lay),
-              "mst_encoder_train_conv1_wgrad: log-mel layout %d does not fit the training kernels of precision mode %d", lay, e->train_f16);
-  MST_REQUIRE(lay != MST_LOGMEL_CM16 || e->train_f16 == 1 || lin->lo, "mst_encoder_train_conv1_wgrad: MST_LOGMEL_CM16 needs the low parts in the split-precision mode");
-  MST_REQUIRE(lay == MST_LOGMEL_REF || ((reinterpret_cast<uintptr_t>(lin->data) | reinterpret_cast<uintptr_t>(lin->lo)) & 15) == 0,
-              "mst_encoder_train_conv1_wgrad: channel-minor log-mel must be 16-byte aligned");
+  if (const int rc = check_logmel_in("mst_encoder_train_conv1_wgrad", lin, mst_encoder_train_layout_supported(e, lay), e->train_f16,
+                                     e->train_f16 != 1, false))
+    return rc;
   const float* logmel = static_cast<const float*>(lin->data);
   MST_REQUIRE(B > 0 && frames >= 20, "mst_encoder_train_conv1_wgrad: bad arguments");
   const TrainLayout T = train_layout(e, B, frames);
@@ -4990,9 +4864,8 @@ int mst_encoder_train_conv1_wgrad_in(const mst_encoder* e, const mst_logmel_in* 
   mst::DetAcc* dwa = reinterpret_cast<mst::DetAcc*>(ws + T.dw_acc);
   const long long ndw = (long long)ns * 32 * 392;
   MST_HIP_CHECK(hipMemsetAsync(dwa, 0, (size_t)ndw * sizeof(mst::DetAcc), st));
-  WgradParams wp{logmel, reinterpret_cast<const float*>(ws + T.y1), dwa, B, ns, T.tr1, T.tc1,
-                 e->cfg.split_size, frames, e->cfg.n_mels * frames, e->cfg.overlap * frames,
-                 (long long)8 * e->cfg.n_mels * frames, 0};
+  WgradParams wp{logmel, reinterpret_cast<const float*>(ws + T.y1), dwa, B, ns, T.tr1, T.tc1};
+  conv1_input_geometry(wp, e, frames);
   const long long total = (long long)ns * B * T.tr1 * T.tc1;
   MST_REQUIRE(total < (1LL << 31), "mst_encoder_train_conv1_wgrad: too many tiles");
   // (20-mel sub-bands: the kernel fits two workgroups per CU -- 126 registers, 44 KB of LDS -- and is launched that wide)
@@ -5000,32 +4873,17 @@ int mst_encoder_train_conv1_wgrad_in(const mst_encoder* e, const mst_logmel_in* 
   const float* unscale = nullptr;
   if (train_bwd16(e)) {   // f16 operands, K = positions x 8 clips (encoder_f16train.inc)
     unscale = reinterpret_cast<const float*>(ws + T.t_bscale);
-    WgradF16Params fp{logmel, reinterpret_cast<const h16x8*>(ws + T.t_dyg1), dwa, nullptr, B, ns, T.tr1, T.tc1,
-                      e->cfg.split_size, frames, e->cfg.n_mels * frames, e->cfg.overlap * frames,
-                      (long long)8 * e->cfg.n_mels * frames, lin->lo, e->cfg.n_mels, e->cfg.overlap};
+    WgradF16Params fp{logmel, reinterpret_cast<const h16x8*>(ws + T.t_dyg1), dwa, nullptr, B, ns, T.tr1, T.tc1};
+    conv1_input_geometry(fp, e, frames);
+    fp.x_lo = lin->lo, fp.cm_mels = e->cfg.n_mels, fp.cm_overlap = e->cfg.overlap;
     const long long items = (long long)ns * ((B + 7) / 8) * T.tr1 * T.tc1;
-    constexpr size_t lds1 = (size_t)(8 * 8 * 46 + 2 * 20 * 64) * 16, lds3 = (size_t)(2 * 8 * 8 * 46 + 2 * 10 * 2 * 64) * 16;
-    static unsigned long long attr_set = 0;   // per-device bit mask: the attribute belongs to the device
-    if (mst::first_use_on_device(attr_set)) {
-      hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_f16_kernel<1, 1>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-      if (err == hipSuccess)
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_f16_kernel<1, 3>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-      if (err == hipSuccess)
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_f16_kernel<1, 1, 2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-      if (err == hipSuccess)
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_f16_kernel<1, 3, 2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-      if (err != hipSuccess) return mst::fail(MST_EHIP, "conv1 wgrad (f16) attribute failed: %s", hipGetErrorString(err));
-    }
     const dim3 gw((int)std::min<long long>(e->num_cus, items));
+    const dim3 blk(kConvThreads);
     if (lay == MST_LOGMEL_CM16) {
-      if (e->train_f16 == 2) hipLaunchKernelGGL((wgrad_f16_kernel<1, 3, 2>), gw, dim3(kConvThreads), lds3, st, fp);
-      else hipLaunchKernelGGL((wgrad_f16_kernel<1, 1, 2>), gw, dim3(kConvThreads), lds1, st, fp);
-    } else if (e->train_f16 == 2) hipLaunchKernelGGL((wgrad_f16_kernel<1, 3>), gw, dim3(kConvThreads), lds3, st, fp);
-    else hipLaunchKernelGGL((wgrad_f16_kernel<1, 1>), gw, dim3(kConvThreads), lds1, st, fp);
+      if (e->train_f16 == 2) MST_HIP_CHECK(mst::launch_lds<wgrad_f16_kernel<1, 3, 2>>(gw, blk, kWgradF16Lds<1, 3>, st, fp));
+      else MST_HIP_CHECK(mst::launch_lds<wgrad_f16_kernel<1, 1, 2>>(gw, blk, kWgradF16Lds<1, 1>, st, fp));
+    } else if (e->train_f16 == 2) MST_HIP_CHECK(mst::launch_lds<wgrad_f16_kernel<1, 3>>(gw, blk, kWgradF16Lds<1, 3>, st, fp));
+    else MST_HIP_CHECK(mst::launch_lds<wgrad_f16_kernel<1, 1>>(gw, blk, kWgradF16Lds<1, 1>, st, fp));
   } else if (e->sub == 2) hipLaunchKernelGGL((conv1_wgrad_kernel<2, 8>), dim3(g8), dim3(512), 0, st, wp);
   else hipLaunchKernelGGL((conv1_wgrad_kernel<1, 8>), dim3(g8), dim3(512), 0, st, wp);
   hipLaunchKernelGGL(det_to_float_kernel, dim3((unsigned)((ndw + 255) / 256)), dim3(256), 0, st, dwa, dw, ndw, unscale);
@@ -5050,9 +4908,8 @@ int mst_encoder_train_conv2_wgrad(const mst_encoder* e, const float* pool1, int 
   mst::DetAcc* dwa = reinterpret_cast<mst::DetAcc*>(ws + T.dw_acc);
   const long long ndw = (long long)ns * 64 * 1568;
   MST_HIP_CHECK(hipMemsetAsync(dwa, 0, (size_t)ndw * sizeof(mst::DetAcc), st));
-  WgradParams wp{pool1, reinterpret_cast<const float*>(ws + T.y2), dwa, B, ns, T.tr2, T.tc2,
-                 e->H1, L.W1, e->H1 * L.W1, 32 * e->H1 * L.W1, (long long)ns * 32 * e->H1 * L.W1,
-                 0};
+  WgradParams wp{pool1, reinterpret_cast<const float*>(ws + T.y2), dwa, B, ns, T.tr2, T.tc2};
+  conv2_input_geometry(wp, e, L.W1);
   const long long total = (long long)ns * B * T.tr2 * T.tc2;
   MST_REQUIRE(total < (1LL << 31), "mst_encoder_train_conv2_wgrad: too many tiles");
   const int g = (int)std::min<long long>(e->num_cus & ~3, 4 * total);   // groups of 4 workgroups (one per input-channel chunk)
@@ -5060,32 +4917,17 @@ int mst_encoder_train_conv2_wgrad(const mst_encoder* e, const float* pool1, int 
   if (train_bwd16(e)) {
     unscale = reinterpret_cast<const float*>(ws + T.t_bscale);
     WgradF16Params fp{pool1, reinterpret_cast<const h16x8*>(ws + T.t_dyg2), dwa, reinterpret_cast<const float*>(ws + T.t_f16scale),
-                      B, ns, T.tr2, T.tc2, e->H1, L.W1, e->H1 * L.W1, 32 * e->H1 * L.W1, (long long)ns * 32 * e->H1 * L.W1,
-                      nullptr, 0, 0};
+                      B, ns, T.tr2, T.tc2};
+    conv2_input_geometry(fp, e, L.W1);
     if (!pool1) fp.x = ws + T.t_pool1_h16, fp.x_lo = ws + T.t_pool1_l16;   // (in_clipstride = elements per clip in either form)
     const long long items = (long long)ns * ((B + 7) / 8) * T.tr2 * T.tc2;
-    constexpr size_t lds1 = (size_t)(8 * 14 * 14 + 4 * 16 * 64) * 16, lds3 = (size_t)(2 * 8 * 14 * 14 + 4 * 8 * 2 * 64) * 16;
-    static unsigned long long attr_set = 0;   // per-device bit mask: the attribute belongs to the device
-    if (mst::first_use_on_device(attr_set)) {
-      hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_f16_kernel<2, 1>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-      if (err == hipSuccess)
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_f16_kernel<2, 3>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-      if (err == hipSuccess)
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_f16_kernel<2, 1, 3>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-      if (err == hipSuccess)
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_f16_kernel<2, 3, 3>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-      if (err != hipSuccess) return mst::fail(MST_EHIP, "conv2 wgrad (f16) attribute failed: %s", hipGetErrorString(err));
-    }
     const dim3 gw((int)std::min<long long>(e->num_cus & ~3, 4 * items));
+    const dim3 blk(kConvThreads);
     if (!pool1) {
-      if (e->train_f16 == 2) hipLaunchKernelGGL((wgrad_f16_kernel<2, 3, 3>), gw, dim3(kConvThreads), lds3, st, fp);
-      else hipLaunchKernelGGL((wgrad_f16_kernel<2, 1, 3>), gw, dim3(kConvThreads), lds1, st, fp);
-    } else if (e->train_f16 == 2) hipLaunchKernelGGL((wgrad_f16_kernel<2, 3>), gw, dim3(kConvThreads), lds3, st, fp);
-    else hipLaunchKernelGGL((wgrad_f16_kernel<2, 1>), gw, dim3(kConvThreads), lds1, st, fp);
+      if (e->train_f16 == 2) MST_HIP_CHECK(mst::launch_lds<wgrad_f16_kernel<2, 3, 3>>(gw, blk, kWgradF16Lds<2, 3>, st, fp));
+      else MST_HIP_CHECK(mst::launch_lds<wgrad_f16_kernel<2, 1, 3>>(gw, blk, kWgradF16Lds<2, 1>, st, fp));
+    } else if (e->train_f16 == 2) MST_HIP_CHECK(mst::launch_lds<wgrad_f16_kernel<2, 3>>(gw, blk, kWgradF16Lds<2, 3>, st, fp));
+    else MST_HIP_CHECK(mst::launch_lds<wgrad_f16_kernel<2, 1>>(gw, blk, kWgradF16Lds<2, 1>, st, fp));
   } else {
     hipLaunchKernelGGL(conv2_wgrad_kernel, dim3(g), dim3(kConvThreads), 0, st, wp);
   }
@@ -5108,40 +4950,21 @@ int mst_encoder_train_conv2_dgrad(const mst_encoder* e, const float* dy2, int B,
   cp.in_clipstride = (long long)64 * H1 * W1;
   cp.out_rows = H1, cp.out_cols = W1;
   cp.tiles_r = (H1 + 1) / 2, cp.tiles_c = (W1 + 39) / 40;
-  cp.sets_per_band = (B * cp.tiles_r * cp.tiles_c + kConvWaves - 1) / kConvWaves;
+  cp.sets_per_band = sets_per_band(B, cp.tiles_r, cp.tiles_c);
   cp.raw_rows = H1, cp.raw_cols = W1, cp.mask = drop1_mask, cp.mask_scale = drop1_scale;
   MST_REQUIRE((long long)cp.in_bandoff * ns < (1LL << 31), "mst_encoder_train_conv2_dgrad: batch too large for 32-bit band offsets");
   const int g = std::min(e->num_cus, ns * cp.sets_per_band);
   if (train_bwd16(e)) {   // dy2 holds f16, channel-minor [n_sub][B][H1][W1][64] (mst_encoder_train_backward_apply in this mode)
-    constexpr size_t lds1 = (size_t)(kF16Steps * 2 * 64 + kConvWaves * 8 * 46) * 16, lds3 = 2 * lds1;
-    static unsigned long long attr_set = 0;   // per-device bit mask: the attribute belongs to the device
-    if (mst::first_use_on_device(attr_set)) {
-      hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_dgrad_f16_kernel<1>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-      if (err == hipSuccess)
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_dgrad_f16_kernel<3>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-      if (err != hipSuccess) return mst::fail(MST_EHIP, "conv2 dgrad (f16) attribute failed: %s", hipGetErrorString(err));
-    }
     cp.f16_winv = e->f16_winv2d;
     const h16x8* dh = reinterpret_cast<const h16x8*>(dy2);
     const h16x8* wf = reinterpret_cast<const h16x8*>(e->w2dfrag16);
+    const dim3 blk(kConvThreads);
     if (e->train_f16 == 2)   // split precision: the low parts follow the high parts, [2][n_sub][B][H1][W1][64]
-      hipLaunchKernelGGL(conv2_dgrad_f16_kernel<3>, dim3(g), dim3(kConvThreads), lds3, st, cp, dh, dh + (size_t)ns * B * H1 * W1 * 8, wf);
-    else hipLaunchKernelGGL(conv2_dgrad_f16_kernel<1>, dim3(g), dim3(kConvThreads), lds1, st, cp, dh, dh, wf);
-    MST_HIP_CHECK(hipGetLastError());
+      MST_HIP_CHECK(mst::launch_lds<conv2_dgrad_f16_kernel<3>>(dim3(g), blk, kConv2DgradF16Lds<3>, st, cp, dh, dh + (size_t)ns * B * H1 * W1 * 8, wf));
+    else MST_HIP_CHECK(mst::launch_lds<conv2_dgrad_f16_kernel<1>>(dim3(g), blk, kConv2DgradF16Lds<1>, st, cp, dh, dh, wf));
     return MST_OK;
   }
-  using GEO = ConvGeom<3, 2>;
-  const size_t lds = (size_t)(2 * GEO::WBP + kConvWaves * GEO::PATCH) * sizeof(float);
-  static unsigned long long attr_set = 0;   // per-device bit mask: the attribute belongs to the device
-  if (mst::first_use_on_device(attr_set)) {
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_kernel<3, 2, 2>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (err != hipSuccess) return mst::fail(MST_EHIP, "conv2 dgrad attribute failed: %s", hipGetErrorString(err));
-  }
-  hipLaunchKernelGGL((conv_kernel<3, 2, 2>), dim3(g), dim3(kConvThreads), lds, st, cp);
-  MST_HIP_CHECK(hipGetLastError());
+  MST_HIP_CHECK(launch_conv<3, 2, 2>(cp, g, st));
   return MST_OK;
 }
 

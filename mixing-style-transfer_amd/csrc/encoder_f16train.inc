@@ -169,6 +169,8 @@ __global__ __launch_bounds__(64) void f16_scale_band_kernel(const float2* __rest
 // Epilogue: raw values (times the inverse weight pre-scale) through the Dropout keep-mask to
 // [clip][band][32][rows][cols], as conv_kernel<3, 2, 2>.
 // ------------------------------------------------------------------------------------------
+template <int TERMS>   // dynamic LDS in 16-byte vectors, hi (and lo: TERMS 3) each: a weight chunk [step][nt][lane] + a patch per wave
+constexpr size_t kConv2DgradF16Lds = (size_t)(TERMS == 3 ? 2 : 1) * (kF16Steps * CC<3, 2>::NT * 64 + kConvWaves * CC<3, 2>::PR * CC<3, 2>::PC) * 16;
 template <int TERMS>
 __global__ __launch_bounds__(kConvThreads) void conv2_dgrad_f16_kernel(const ConvParams p, const h16x8* __restrict__ dy_hi,
                                                                       const h16x8* __restrict__ dy_lo,
@@ -443,6 +445,8 @@ struct WgradF16Params {
 // LAY 3: (LAYER 2) x = the range-scaled float16 pool1 the training forward wrote for conv2, [B][nsub][rows][cols][32] (+ low
 //        parts in x_lo): the same one-position-per-thread loader on this workgroup's 8-channel chunk; the fp32 pool1 is not
 //        needed at all (the forward pass then does not write it).
+template <int LAYER, int TERMS>   // dynamic LDS in 16-byte vectors: the patch [hi(/lo)][8 ci][PR][PC] + the dy vectors [MTN][NV][64]
+constexpr size_t kWgradF16Lds = (size_t)((TERMS == 3 ? 2 : 1) * 8 * (LAYER == 1 ? 8 * 46 : 14 * 14) + (LAYER == 1 ? 2 * 20 : 4 * 16) * 64) * 16;
 template <int LAYER, int TERMS, int LAY = 0>
 __global__ __launch_bounds__(kConvThreads) void wgrad_f16_kernel(const WgradF16Params p) {
   static_assert(LAY == 0 || (LAY == 2 && LAYER == 1) || (LAY == 3 && LAYER == 2),

@@ -1032,24 +1032,12 @@ __global__ __launch_bounds__(256) void melfeat_finalize_kernel(const FParams p) 
 
 template <int NFFT, int NB, typename ST>
 hipError_t launch_melfeat(const KParams& kp, int grid, size_t lds, hipStream_t st) {
-  {   // dynamic-LDS limit: a per-device attribute, set on every launch (a cheap driver call)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(melfeat_kernel<NFFT, NB, ST>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((melfeat_kernel<NFFT, NB, ST>), dim3(grid), dim3(kThreads), lds, st, kp);
-  return hipGetLastError();
+  return mst::launch_lds<melfeat_kernel<NFFT, NB, ST>>(dim3(grid), dim3(kThreads), lds, st, kp);
 }
 
 template <int NFFT, typename ST, int WPS>
 hipError_t launch_melfeat_spw(const KParams& kp, int grid, size_t lds, hipStream_t st) {
-  {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(melfeat_spw_kernel<NFFT, ST, WPS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((melfeat_spw_kernel<NFFT, ST, WPS>), dim3(grid), dim3(SpwGeom<WPS>::THREADS), lds, st, kp);
-  return hipGetLastError();
+  return mst::launch_lds<melfeat_spw_kernel<NFFT, ST, WPS>>(dim3(grid), dim3(SpwGeom<WPS>::THREADS), lds, st, kp);
 }
 
 template <int NFFT>

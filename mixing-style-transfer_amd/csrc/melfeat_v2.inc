@@ -489,11 +489,7 @@ __global__ __launch_bounds__(WPS * 256) void melfeat_v2_kernel(const K2Params p)
 
 template <typename ST, int WPS, int NBL, bool CM, bool STD = false>
 hipError_t launch_melfeat_v2_cm(const K2Params& kp, int grid, size_t lds, hipStream_t st) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(melfeat_v2_kernel<ST, WPS, NBL, CM, STD>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   // per device: set every time
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((melfeat_v2_kernel<ST, WPS, NBL, CM, STD>), dim3(grid), dim3(WPS * 256), lds, st, kp);
-  return hipGetLastError();
+  return mst::launch_lds<melfeat_v2_kernel<ST, WPS, NBL, CM, STD>>(dim3(grid), dim3(WPS * 256), lds, st, kp);
 }
 // std_table: the plan's piece table has the standard shape (see STD above); used by the channel-minor builds of the 12-wave kernel
 template <typename ST, int WPS, int NBL = 2>

@@ -439,11 +439,7 @@ __global__ __launch_bounds__(512) void melfeat_v2_2048_kernel(const K4Params p) 
 
 template <typename ST, bool CM>
 hipError_t launch_melfeat_v2_2048_cm(const K4Params& kp, int grid, size_t lds, hipStream_t st) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(melfeat_v2_2048_kernel<ST, CM>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((melfeat_v2_2048_kernel<ST, CM>), dim3(grid), dim3(512), lds, st, kp);
-  return hipGetLastError();
+  return mst::launch_lds<melfeat_v2_2048_kernel<ST, CM>>(dim3(grid), dim3(512), lds, st, kp);
 }
 template <typename ST>
 hipError_t launch_melfeat_v2_2048(const K4Params& kp, int grid, size_t lds, hipStream_t st) {

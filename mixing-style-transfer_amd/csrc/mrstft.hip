@@ -367,19 +367,12 @@ int log2_exact(int v) {
 
 template <int N>
 hipError_t launch_fwd(const FwdParams& p, int grid, hipStream_t st) {
-  const size_t lds = Geo<N>::kLds;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrstft_fwd_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((mrstft_fwd_kernel<N>), dim3(grid), dim3(kThreads), lds, st, p);
-  return hipGetLastError();
+  return mst::launch_lds<mrstft_fwd_kernel<N>>(dim3(grid), dim3(kThreads), Geo<N>::kLds, st, p);
 }
 template <int N>
 hipError_t launch_bwd(const BwdParams& p, int grid, hipStream_t st) {
   const size_t lds = Geo<N>::kLds + (size_t)(kRound + p.R - 1) * p.hop * sizeof(float);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrstft_bwd_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((mrstft_bwd_kernel<N>), dim3(grid), dim3(kThreads), lds, st, p);
-  return hipGetLastError();
+  return mst::launch_lds<mrstft_bwd_kernel<N>>(dim3(grid), dim3(kThreads), lds, st, p);
 }
 
 size_t acc_bytes(int n_res) { return mst::align_up((size_t)3 * n_res * sizeof(mst::DetAcc), 256); }
@@ -654,9 +647,7 @@ int launch_logmel_bwd(LogmelBwdParams& p, hipStream_t st) {
   p.blocks_per_row = (p.nchunks + p.cpb - 1) / p.cpb;
   const long long grid = (long long)p.rows * p.blocks_per_row;
   MST_REQUIRE(grid < (1LL << 31), "mst_logmel_backward: %lld workgroups", grid);
-  MST_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_bwd_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((logmel_bwd_kernel<N>), dim3((unsigned)grid), dim3(kThreads), lds, st, p);
-  MST_HIP_CHECK(hipGetLastError());
+  MST_HIP_CHECK(mst::launch_lds<logmel_bwd_kernel<N>>(dim3((unsigned)grid), dim3(kThreads), lds, st, p));
   return MST_OK;
 }
 

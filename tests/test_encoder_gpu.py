@@ -71,8 +71,15 @@ def close_f16(a, ref, tol=1e-4, frac=5e-4, hard=5e-3, name=None):
 
 
 @pytest.mark.parametrize("tag,cfg,T", [("default", cases.CFG_DEFAULT, 441000), ("cfg2", cases.CFG_BASELINE_SH, 441000),
-                                        ("default_short", cases.CFG_DEFAULT, 66150)])
-def test_encoder_vs_golden_and_oracle(tag, cfg, T):
+                                        ("default_short", cases.CFG_DEFAULT, 66150),
+                                        # "+chunked": conv1 on the chunked kernel (MST_CONV1_CHUNKED, read per launch):
+                                        # conv_kernel<1, 2, 0> (20-mel sub-bands) and conv_kernel<1, 1, 0> (16-mel)
+                                        ("default_short+chunked", cases.CFG_DEFAULT, 66150),
+                                        ("cfg2+chunked", cases.CFG_BASELINE_SH, 441000)])
+def test_encoder_vs_golden_and_oracle(tag, cfg, T, monkeypatch):
+    tag, _, variant = tag.partition("+")
+    if variant == "chunked":
+        monkeypatch.setenv("MST_CONV1_CHUNKED", "1")
     g = np.load(os.path.join(G, "encoder.npz"))
     model, sd = build_model(cfg)
     x = torch.stack([cases.synth_clip(c, T) for c in (0, 1)], 0)

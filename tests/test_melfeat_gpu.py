@@ -220,14 +220,22 @@ def test_sub_methods_and_errors():
     (dict(n_fft=2048, hop_length=512, n_mels=80), 66150),        # generic kernel, even/odd packed FFT
     (dict(n_fft=1024, hop_length=256, n_mels=256), 44100),       # generic kernel, 4 band slots
     (dict(n_fft=512, hop_length=128, n_mels=64), 30001),         # odd length: scalar loads
+    # `env`: the switches that select the older / narrower builds (read per launch; MST_V2_WPS when the plan is made)
+    (dict(env={"MST_STAGE_A": "spw"}), 44100),                             # melfeat_spw_kernel<1024, *, 3>
+    (dict(env={"MST_STAGE_A": "spw", "MST_SPW_WPS": "2"}), 44100),         # melfeat_spw_kernel<1024, *, 2>
+    (dict(n_fft=512, hop_length=128, n_mels=64, env={}), 30000),           # melfeat_spw_kernel<512, *, 2> (vector loads)
+    (dict(env={"MST_V2_WPS": "2"}), 44100),                                # melfeat_v2_kernel<*, 2, 2>
 ])
-def test_pcm16_input_is_bit_identical_to_fp32_of_the_same_samples(kw, T):
+def test_pcm16_input_is_bit_identical_to_fp32_of_the_same_samples(kw, T, monkeypatch):
     """int16 PCM ingest: the kernels convert s * 2^-15 exactly, so features and log-mel must EQUAL the
     fp32 entry point run on float(pcm) / 32768 -- packed (B,8,T) tensor and the collate-style dict of views."""
     from mst_amd import ingest
     x = torch.stack([cases.synth_clip(c, T) for c in (2, 4)], 0)
     q = ingest.float_to_pcm16(x)
     xf = q.float() / 32768.0
+    kw = dict(kw)
+    for k, v in kw.pop("env", {}).items():
+        monkeypatch.setenv(k, v)
     ext = fe(**kw)
     f0, lm0 = run(xf, ext)
     lm1, f1 = ext.plan().forward(q.cuda())
