@@ -63,6 +63,20 @@ int upload(T** dst, const T* host, size_t n) {
   return MST_OK;
 }
 
+// Owner of one device buffer: move-only, hipFree in the destructor (hipFree(nullptr) is a no-op).
+template <typename T>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  ~DevBuf() { (void)hipFree(p_); }
+  int upload(const T* host, size_t n) { return (void)hipFree(p_), ::mst::upload(&p_, host, n); }
+  T* get() const { return p_; }
+
+ private:
+  T* p_ = nullptr;
+};
+
 // Blocks b and b+8 share an XCD (round-robin dispatch): give every XCD a contiguous run of
 // logical work items so neighbouring tiles hit the same L2.  Bijective for any grid size.
 __device__ __forceinline__ int xcd_remap(int bid, int nblk) {

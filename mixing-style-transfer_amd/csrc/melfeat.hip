@@ -19,9 +19,11 @@
 #include "common.h"
 #include "fft_wave.h"
 #include "fft_pk.h"
+#include "stage_a_tables.h"
 
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <vector>
 
 
@@ -53,9 +55,13 @@ enum : int {
   S_NFRAME = 66,  // [1] frames in this run
 };
 
-struct LaneBand {  // one mel band owned by a lane: band id (-1 = none) and first bin of its support
-  int band, start;
-};
+using stage_a::LaneBand;
+
+// Every kernel below has ONE description of its dynamic LDS: a layout struct beside it with the byte offset of each area and
+// the total bytes(), which the launch passes.  Offsets are compile-time constants (the kernels' table reads fold them into
+// their addresses); areas behind one whose length is known at run time only are named a_* and count from THAT area's end.
+constexpr size_t kMaxLds = 160 * 1024;   // LDS of a workgroup
+constexpr int pad4(int n) { return (n + 3) & ~3; }
 
 struct KParams {
   const void* stem[4];       // per-stem base pointers (float or int16 PCM), each [B][2][T], clip stride `clip_stride` samples
@@ -323,21 +329,37 @@ __device__ __forceinline__ void frames_mel_cplx(const KParams& p, const ST* __re
   }
 }
 
+// LDS of melfeat_kernel<NFFT, ..>; a_*: from the end of tw[twn].  The output tile [tile_bufs][2*M][kTileStride] follows melw.
+template <int NFFT>
+struct GenericLds {
+  static constexpr int NC = NFFT / 2, SCR = nf_of(NFFT) * (NC + NC / 8);   // SCR: padded float2 per wave
+  static constexpr bool PAIR = NFFT <= 1024;                  // frame-pair packed full-length FFT (see frames_mel_cplx)
+  // float2 win[NC] (window pairs = [NFFT] floats), tw[twn], twn = PAIR ? tw2_count : tw_count
+  static constexpr int win = 0, tw = win + NC * 8;
+  // float2 post[NC] (even/odd packing only), scr[kWaves][SCR] (the workgroup reductions alias it); float melw[pad4(nnz)]
+  static constexpr int a_post = 0, a_scr = a_post + (PAIR ? 0 : NC * 8), a_melw = a_scr + kWaves * SCR * 8;
+  static constexpr size_t bytes(int tw_count, int tw2_count, int nnz, int M, int tile_bufs) {
+    return (size_t)tw + (size_t)(PAIR ? tw2_count : tw_count) * 8 + a_melw + (size_t)pad4(nnz) * 4 + (size_t)tile_bufs * 2 * M * kTileStride * 4;
+  }
+  // floats of the spectral reduction: per wave 4 stems x 4 band slots x 64 lanes + 12 scalars
+  static_assert(kWaves * 4 * 4 * 64 + kWaves * 12 <= 2 * kWaves * SCR, "the reduction buffer must fit the FFT scratch");
+};
+
 template <int NFFT, int NB, typename ST>
 __global__ __launch_bounds__(kThreads) void melfeat_kernel(const KParams p) {
-  constexpr int NC = NFFT / 2;
-  constexpr int NF = nf_of(NFFT);            // FFTs a wave runs side by side
-  constexpr int SCR = NF * (NC + NC / 8);    // padded float2 per wave
+  using L = GenericLds<NFFT>;
+  constexpr int NC = L::NC, SCR = L::SCR;
+  constexpr bool PAIR = L::PAIR;
   constexpr float kLn2 = 0.69314718055994530942f;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr bool PAIR = NFFT <= 1024;        // frame-pair packed full-length FFT (see frames_mel_pair)
   const int twn = PAIR ? p.tw2_count : p.tw_count;
-  float2* s_win = reinterpret_cast<float2*>(smem);           // [NC] float2 = window pairs = [NFFT] floats
-  float2* s_tw = s_win + NC;                                   // [twn]
-  float2* s_post = s_tw + twn;                                 // [NC] (even/odd packing only)
-  float2* s_scr = s_post + (PAIR ? 0 : NC);                    // [kWaves][SCR]
-  float* s_melw = reinterpret_cast<float*>(s_scr + kWaves * SCR);  // [nnz padded to 4]
-  float* s_tile0 = s_melw + ((p.nnz + 3) & ~3);                // [2][2*M][kTileStride] double-buffered output tile
+  float2* s_win = reinterpret_cast<float2*>(smem + L::win);
+  float2* s_tw = reinterpret_cast<float2*>(smem + L::tw);
+  unsigned char* after_tw = reinterpret_cast<unsigned char*>(s_tw + twn);
+  float2* s_post = reinterpret_cast<float2*>(after_tw + L::a_post);
+  float2* s_scr = reinterpret_cast<float2*>(after_tw + L::a_scr);
+  float* s_melw = reinterpret_cast<float*>(after_tw + L::a_melw);
+  float* s_tile0 = s_melw + pad4(p.nnz);   // double-buffered unless p.tile_bufs == 1
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int work = mst::xcd_remap(blockIdx.x, gridDim.x);
@@ -657,18 +679,33 @@ struct SpwGeom {
   static constexpr int TF = WPS * FPW;             // frames per batch
 };
 
+// LDS of melfeat_spw_kernel<NFFT, ., WPS>; a_*: from the end of tw2[tw2_count].  The log-mel tile [TF][8*M + 1] follows melw.
+template <int NFFT, int WPS>
+struct SpwLds {
+  using G = SpwGeom<WPS>;
+  static constexpr int SCR = NFFT + NFFT / 8;                     // float2 per wave
+  // float winf[NFFT]; float2 tw2[tw2_count] | float2 scr[WAVES][SCR] (the final reduction aliases it); float melw[pad4(nnz)]
+  static constexpr int winf = 0, tw2 = winf + NFFT * 4, a_scr = 0, a_melw = a_scr + G::WAVES * SCR * 8;
+  static constexpr size_t bytes(int tw2_count, int nnz, int M) {
+    return (size_t)tw2 + (size_t)tw2_count * 8 + a_melw + (size_t)pad4(nnz) * 4 + (size_t)G::TF * (8 * M + 1) * 4;
+  }
+  static_assert(G::WAVES * 2 * 64 + G::WAVES * 24 <= 2 * G::WAVES * SCR, "the reduction buffer must fit the FFT scratch");
+};
+
 template <int NFFT, typename ST, int WPS>
 __global__ __launch_bounds__(SpwGeom<WPS>::THREADS) void melfeat_spw_kernel(const KParams p) {
   constexpr int kWaves = SpwGeom<WPS>::WAVES, kThreads = SpwGeom<WPS>::THREADS, kTF = SpwGeom<WPS>::TF;
   constexpr int NB = 2, NOWN = NFFT / 256;
-  constexpr int SCR = NFFT + NFFT / 8;
+  using L = SpwLds<NFFT, WPS>;
+  constexpr int SCR = L::SCR;
   constexpr float kLn2 = 0.69314718055994530942f;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* s_winf = reinterpret_cast<float*>(smem);                 // [NFFT]
-  float2* s_tw2 = reinterpret_cast<float2*>(s_winf + NFFT);       // [tw2_count]
-  float2* s_scr = s_tw2 + p.tw2_count;                            // [kWaves][SCR]
-  float* s_melw = reinterpret_cast<float*>(s_scr + kWaves * SCR);
-  float* s_tile = s_melw + ((p.nnz + 3) & ~3);                    // [kTF][8*M + 1]  log-mel, frame-major
+  float* s_winf = reinterpret_cast<float*>(smem + L::winf);
+  float2* s_tw2 = reinterpret_cast<float2*>(smem + L::tw2);
+  unsigned char* after_tw2 = reinterpret_cast<unsigned char*>(s_tw2 + p.tw2_count);
+  float2* s_scr = reinterpret_cast<float2*>(after_tw2 + L::a_scr);
+  float* s_melw = reinterpret_cast<float*>(after_tw2 + L::a_melw);
+  float* s_tile = s_melw + pad4(p.nnz);   // frame-major
   const int M = p.M, TS = 8 * M + 1;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -894,13 +931,22 @@ __device__ double pearson_vs_index(const double* y, int n, int lane) {
   return fmin(1.0, fmax(-1.0, c));      // torch.corrcoef clips to [-1, 1]
 }
 
+// LDS of melfeat_finalize_kernel, all doubles: band[4*M] mean dB per band, then (a_*: from its end) the reduced scalars
+// sc[kNumScalars], chmean[8], chm2[8], cross[4 padded to 8] and the resampled band curves curve[4][detailed_bins]
+struct FinalizeLds {
+  static constexpr int a_sc = 0, a_chmean = a_sc + kNumScalars * 8, a_chm2 = a_chmean + 64, a_cross = a_chm2 + 64, a_curve = a_cross + 64;
+  static constexpr size_t bytes(int M, int detailed_bins) { return (size_t)4 * M * 8 + a_curve + (size_t)4 * (detailed_bins > 0 ? detailed_bins : 0) * 8; }
+};
+
 __global__ __launch_bounds__(256) void melfeat_finalize_kernel(const FParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  double* band = reinterpret_cast<double*>(smem);  // [4*M] mean dB per band
-  double* sc = band + 4 * p.M;                      // [kNumScalars] reduced scalars
-  double* chmean = sc + kNumScalars;                // [8]
-  double* chm2 = chmean + 8;                        // [8]
-  double* cross = chm2 + 8;                         // [4]
+  using L = FinalizeLds;
+  double* band = reinterpret_cast<double*>(smem);
+  unsigned char* after_band = reinterpret_cast<unsigned char*>(band + 4 * p.M);
+  double* sc = reinterpret_cast<double*>(after_band + L::a_sc);
+  double* chmean = reinterpret_cast<double*>(after_band + L::a_chmean);
+  double* chm2 = reinterpret_cast<double*>(after_band + L::a_chm2);
+  double* cross = reinterpret_cast<double*>(after_band + L::a_cross);
   const int tid = threadIdx.x, clip = blockIdx.x, M = p.M;
   const float* base = p.partials + (size_t)clip * p.runs_per_clip * p.pstride;
   const double inv_n_db = 1.0 / (2.0 * p.F);
@@ -1004,7 +1050,7 @@ __global__ __launch_bounds__(256) void melfeat_finalize_kernel(const FParams p) 
       put(o + 4, flat);
     } else {
       const int nb = p.detailed_bins;
-      double* curve = reinterpret_cast<double*>(smem) + 4 * M + kNumScalars + 24 + s * nb;
+      double* curve = reinterpret_cast<double*>(after_band + L::a_curve) + s * nb;
       for (int i = lane; i < nb; i += 64) {
         if (nb >= M) { curve[i] = e[i]; continue; }
         const float scale = nb > 1 ? (float)(M - 1) / (float)(nb - 1) : 0.f;  // align_corners=True
@@ -1030,18 +1076,23 @@ __global__ __launch_bounds__(256) void melfeat_finalize_kernel(const FParams p) 
   }
 }
 
+// THE launch of a stage-A kernel: `lds` is the bytes() of the kernel's layout struct
+template <auto Kernel, typename Params>
+int launch_stage_a(const Params& kp, int grid, int threads, size_t lds, hipStream_t st) {
+  MST_REQUIRE(lds <= kMaxLds, "mst_melfeat_forward: LDS %zu B exceeds 160 KiB", lds);
+  const hipError_t e = mst::launch_lds<Kernel>(dim3(grid), dim3(threads), lds, st, kp);
+  if (e != hipSuccess) return mst::fail(MST_EHIP, "stage-A kernel launch failed: %s", hipGetErrorString(e));
+  return MST_OK;
+}
+
 template <int NFFT, int NB, typename ST>
-hipError_t launch_melfeat(const KParams& kp, int grid, size_t lds, hipStream_t st) {
-  return mst::launch_lds<melfeat_kernel<NFFT, NB, ST>>(dim3(grid), dim3(kThreads), lds, st, kp);
+int launch_melfeat(const KParams& kp, int grid, hipStream_t st) {
+  return launch_stage_a<melfeat_kernel<NFFT, NB, ST>>(kp, grid, kThreads, GenericLds<NFFT>::bytes(kp.tw_count, kp.tw2_count, kp.nnz, kp.M, kp.tile_bufs), st);
 }
-
 template <int NFFT, typename ST, int WPS>
-hipError_t launch_melfeat_spw(const KParams& kp, int grid, size_t lds, hipStream_t st) {
-  return mst::launch_lds<melfeat_spw_kernel<NFFT, ST, WPS>>(dim3(grid), dim3(SpwGeom<WPS>::THREADS), lds, st, kp);
+int launch_melfeat_spw(const KParams& kp, int grid, hipStream_t st) {
+  return launch_stage_a<melfeat_spw_kernel<NFFT, ST, WPS>>(kp, grid, SpwGeom<WPS>::THREADS, SpwLds<NFFT, WPS>::bytes(kp.tw2_count, kp.nnz, kp.M), st);
 }
-
-template <int NFFT>
-constexpr int tw_count_of() { return FftPlan<NFFT / 2>::TW; }
 
 #include "melfeat_v2.inc"
 #include "melfeat_v2_2048.inc"
@@ -1051,58 +1102,45 @@ constexpr int tw_count_of() { return FftPlan<NFFT / 2>::TW; }
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
+static_assert(sizeof(stage_a::F2) == sizeof(float2), "stage_a_tables.h's pairs are uploaded as float2");
+
 struct mst_plan {
   int sr, n_fft, hop, n_mels, detailed_bins, feat_dim;
-  int nc, nb, nnz, tw_count;
-  int glen[4], goff[4];
-  int batches_per_run;
-  float* d_window = nullptr;
-  float2* d_tw = nullptr;
-  float2* d_tw2 = nullptr;
-  int tw2_count = 0;
-  float2* d_post = nullptr;
-  float* d_melw = nullptr;
-  LaneBand* d_lanebands = nullptr;
-  // sliding-window kernel (melfeat_v2.inc): packed-FFT twiddles and the segment form of the sparse mel table
-  bool v2_ok = false;
-  int v2_nslot = 0, v2_glen[kV2Slots] = {0}, v2_goff[kV2Slots] = {0}, v2_segw_count = 0, v2_wps = 3, v2_maxcnt = 1;
-  int2* d_v2_bandtab = nullptr;
-  // n_fft 2048 / hop 512 variant (melfeat_v2_2048.inc): W_2048 combine twiddles and the piece form of the mel table
-  bool v4_ok = false;
-  int v4_nslot = 0, v4_glen[4] = {0, 0, 0, 0}, v4_goff[4] = {0, 0, 0, 0}, v4_segw_count = 0, v4_maxcnt = 0;
-  float2* d_v4_tw4 = nullptr;
-  float2* d_v4_segw = nullptr;
-  int* d_v4_pstart = nullptr;
-  int* d_v4_pid = nullptr;
-  int* d_v4_bandtab = nullptr;
-  float2* d_v2_tw2 = nullptr;
-  float2* d_v2_tw3 = nullptr;
-  float2* d_v2_segw = nullptr;
-  int* d_v2_segstart = nullptr;
-  int* d_v2_segid = nullptr;
+  int batches_per_run;   // StageAEnv::batches_per_run at creation
+  mst::DevBuf<float> window;
+  struct {   // melfeat_kernel, melfeat_spw_kernel: wave-FFT twiddles and the lane-band form of the mel table
+    int nb, nnz, tw_count, tw2_count, glen[4], goff[4];
+    mst::DevBuf<float2> tw, tw2, post;   // tw2: the n_fft-point complex FFT (frame-pair packing, n_fft <= 1024)
+    mst::DevBuf<float> melw;
+    mst::DevBuf<LaneBand> lanebands;
+  } gen;
+  struct {   // melfeat_v2_kernel (1024 / 256) or melfeat_v2_2048_kernel (2048 / 512), if `ok`: packed-FFT twiddles shared by both (tw4: 2048) and the piece table
+    bool ok = false;
+    int wps = 3;   // waves per stem
+    int nslot = 0, maxcnt = 0, segw_count = 0, glen[kV2Slots] = {0}, goff[kV2Slots] = {0};
+    mst::DevBuf<float2> tw2, tw3, tw4, segw;
+    mst::DevBuf<int> start, id, bandtab;   // bandtab: int2 [256] (1024) or int [128] (2048)
+  } sw;
 };
 
 namespace {
 
-void add_pass_tw(std::vector<float2>& tw, int NC, int R, int NS) {
-  if (NS == 1) return;
-  const int nbf = NS <= 64 ? 1 : NC / R / 64;  // (lane + 64 u) % NS does not depend on u when NS divides 64
-  for (int u = 0; u < nbf; ++u)
-    for (int t = 1; t < R; ++t)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int j = lane + 64 * u, k = j % NS;
-        const double a = -2.0 * M_PI * (double)(k * t) / (double)(NS * R);
-        tw.push_back(make_float2((float)cos(a), (float)sin(a)));
-      }
-}
-
-std::vector<std::pair<int, int>> passes_of(int NC) {
-  switch (NC) {
-    case 256: return {{4, 1}, {4, 4}, {4, 16}, {4, 64}};
-    case 512: return {{8, 1}, {8, 8}, {8, 64}};
-    case 1024: return {{8, 1}, {8, 8}, {4, 64}, {4, 256}};
-  }
-  return {};
+// The environment switches of stage A.  mst_plan_create takes batches_per_run and v2_wps2; every forward (and
+// mst_plan_layout_supported) reads the others anew, so they can change between calls.
+struct StageAEnv {
+  int batches_per_run, spw_wps;   // MST_MELFEAT_BATCHES=n: n*16-frame runs of the older kernels (probes; 0: by clip length); MST_SPW_WPS (3)
+  bool v2_wps2, generic, v2_nostd;   // MST_V2_WPS=2: 8-wave melfeat_v2_kernel; MST_MELFEAT_GENERIC: melfeat_kernel only; MST_V2_NOSTD
+  bool old_kernels;      // MST_STAGE_A=spw | generic, or `generic`: no sliding-window kernel
+};
+StageAEnv read_stage_a_env() {
+  auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+  const char* a = getenv("MST_STAGE_A");
+  StageAEnv s;
+  s.batches_per_run = getenv("MST_MELFEAT_BATCHES") ? std::max(1, num("MST_MELFEAT_BATCHES", 0)) : 0;
+  s.spw_wps = num("MST_SPW_WPS", 3);
+  s.v2_wps2 = num("MST_V2_WPS", 0) == 2, s.generic = getenv("MST_MELFEAT_GENERIC"), s.v2_nostd = getenv("MST_V2_NOSTD");
+  s.old_kernels = s.generic || (a && (!strcmp(a, "spw") || !strcmp(a, "generic")));
+  return s;
 }
 
 // Frames per workgroup ("run").  Every workgroup costs about (frames + 2) frame-times and the device executes them in
@@ -1110,182 +1148,29 @@ std::vector<std::pair<int, int>> passes_of(int NC) {
 // the 256 CUs: 72 clips of 1723 frames -> 54-frame runs, 2304 workgroups = 9.0 rounds (486 frame-times per CU; fixed
 // 32-frame runs took 16 rounds = 512).  The run length depends on the clip length only -- never on the batch size --
 // so a clip's partial sums, and with them its features, are bit-identical whatever its batch neighbours are.
-// MST_MELFEAT_BATCHES=n forces n*16-frame runs (used by the probes).
-int frames_per_run_of(const mst_plan* p, int /*B*/, int F) {
+int frames_per_run_of(const mst_plan* p, int F) {
   if (p->batches_per_run > 0) return p->batches_per_run * kTF;
   int fpr = (F + 31) / 32;
   fpr += fpr & 1;
   return std::max(2 * kTF, fpr);
 }
-int runs_per_clip(const mst_plan* p, int B, int F) {
-  const int fpr = frames_per_run_of(p, B, F);
+int runs_per_clip(const mst_plan* p, int F) {
+  const int fpr = frames_per_run_of(p, F);
   return (F + fpr - 1) / fpr;
 }
 int pstride_of(const mst_plan* p) { return 4 * p->n_mels + kNumScalars; }
 
-// sliding-window kernel: frames per wave and runs per clip (a run is WPS * fpw frames; like frames_per_run_of, a
-// function of the clip length only, never of the batch size)
-int v2_fpw(const mst_plan* p, int F) { return std::max(1, ((F + 31) / 32 + p->v2_wps - 1) / p->v2_wps); }
-int v2_runs(const mst_plan* p, int F) {
-  const int fpr = p->v2_wps * v2_fpw(p, F);
+// sliding-window kernels: frames per wave and runs per clip (a run is wps * fpw frames: a function of the clip length only)
+int sw_fpw(const mst_plan* p, int F) { return std::max(1, ((F + 31) / 32 + p->sw.wps - 1) / p->sw.wps); }
+int sw_runs(const mst_plan* p, int F) {
+  const int fpr = p->sw.wps * sw_fpw(p, F);
   return (F + fpr - 1) / fpr;
-}
-
-// seg(k), falling weight wl(k) (band seg - 1) and rising weight wh(k) (band seg) of every bin; false unless every bin feeds
-// at most two ADJACENT bands and the segments are contiguous bin ranges.
-bool segment_bins(const float* fb, int n_bins, int M, std::vector<int>& seg, std::vector<float>& wl, std::vector<float>& wh) {
-  std::vector<int> peak(M, -1);
-  for (int m = 0; m < M; ++m) {
-    float best = 0.f;
-    for (int k = 0; k < n_bins; ++k)
-      if (fb[(size_t)k * M + m] > best) best = fb[(size_t)k * M + m], peak[m] = k;
-  }
-  seg.assign(n_bins, 0), wl.assign(n_bins, 0.f), wh.assign(n_bins, 0.f);
-  int prev = 0;
-  for (int k = 0; k < n_bins; ++k) {
-    int b0 = -1, b1 = -1, cnt = 0;
-    for (int m = 0; m < M; ++m)
-      if (fb[(size_t)k * M + m] != 0.0f) {
-        if (cnt == 0) b0 = m;
-        b1 = m;
-        ++cnt;
-      }
-    if (cnt > 2 || (cnt == 2 && b1 != b0 + 1)) return false;
-    int s = prev;
-    if (cnt == 2) {
-      s = b1, wl[k] = fb[(size_t)k * M + b0], wh[k] = fb[(size_t)k * M + b1];
-    } else if (cnt == 1) {
-      if (k <= peak[b0]) s = b0, wh[k] = fb[(size_t)k * M + b0];
-      else s = b0 + 1, wl[k] = fb[(size_t)k * M + b0];
-    }
-    if (s < prev) return false;
-    seg[k] = prev = s;
-  }
-  return true;
-}
-
-// Piece form for melfeat_v2_2048_kernel: segments cut into pieces of at most 16 bins (numbered in segment order, so the
-// pieces of a segment are consecutive), pieces dealt to (slot, lane) by length, and per band the piece ranges of its
-// rising segment (b) and of its falling segment (b + 1).
-bool v4_build_pieces(mst_plan* p, const float* fb, std::vector<float2>& segw, std::vector<int>& pstart, std::vector<int>& pid,
-                     std::vector<int>& bandtab) {
-  const int M = p->n_mels, n_bins = p->n_fft / 2 + 1;
-  if (p->n_fft != 2048 || M > 128) return false;
-  std::vector<int> seg;
-  std::vector<float> wl, wh;
-  if (!segment_bins(fb, n_bins, M, seg, wl, wh)) return false;
-  const int nseg = M + 1;
-  std::vector<int> start(nseg, 0), len(nseg, 0);
-  for (int k = n_bins - 1; k >= 0; --k) start[seg[k]] = k, ++len[seg[k]];
-  struct Piece { int start, len; };
-  std::vector<Piece> pieces;
-  std::vector<int> first(nseg, 0), cnt(nseg, 0);
-  for (int sg = 0; sg < nseg; ++sg) {
-    first[sg] = (int)pieces.size();
-    for (int o = 0; o < len[sg]; o += 16) pieces.push_back({start[sg] + o, std::min(16, len[sg] - o)}), ++cnt[sg];
-  }
-  const int np = (int)pieces.size();
-  if (np > 135) return false;   // exchange arrays hold 136 entries, the last one is the dump slot
-  std::vector<int> order(np);
-  for (int i = 0; i < np; ++i) order[i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pieces[a].len > pieces[b].len; });
-  p->v4_nslot = (np + 63) / 64;
-  if (p->v4_nslot > 4) return false;
-  pstart.assign((size_t)p->v4_nslot * 64, 0);
-  pid.assign((size_t)p->v4_nslot * 64, 135);
-  int off = 0;
-  for (int r = 0; r < p->v4_nslot; ++r) {
-    int gl = 0;
-    for (int lane = 0; lane < 64 && r * 64 + lane < np; ++lane) gl = std::max(gl, pieces[order[r * 64 + lane]].len);
-    p->v4_glen[r] = gl, p->v4_goff[r] = off;
-    segw.resize((size_t)(off + gl) * 64, make_float2(0.f, 0.f));
-    for (int lane = 0; lane < 64 && r * 64 + lane < np; ++lane) {
-      const int pc = order[r * 64 + lane];
-      pstart[(size_t)r * 64 + lane] = pieces[pc].start, pid[(size_t)r * 64 + lane] = pc;
-      for (int i = 0; i < pieces[pc].len; ++i)
-        segw[(size_t)(off + i) * 64 + lane] = make_float2(wl[pieces[pc].start + i], wh[pieces[pc].start + i]);
-    }
-    off += gl;
-  }
-  if (segw.size() & 1) segw.push_back(make_float2(0.f, 0.f));
-  if (segw.empty()) segw.resize(2, make_float2(0.f, 0.f));
-  p->v4_segw_count = (int)segw.size();
-  bandtab.assign(128, 0);
-  p->v4_maxcnt = 0;
-  for (int b = 0; b < M; ++b) {
-    bandtab[(b >> 6) * 64 + (b & 63)] = first[b] | (cnt[b] << 8) | (first[b + 1] << 16) | (cnt[b + 1] << 24);
-    p->v4_maxcnt = std::max(p->v4_maxcnt, std::max(cnt[b], cnt[b + 1]));
-  }
-  return true;
-}
-int v4_fpw(int F) { return std::max(1, ((F + 31) / 32 + 1) / 2); }
-int v4_runs(int F) {
-  const int fpr = 2 * v4_fpw(F);
-  return (F + fpr - 1) / fpr;
-}
-
-// Piece form of the triangular filterbank for melfeat_v2_kernel (n_fft 1024).  Every bin k feeds at most two ADJACENT
-// bands: the falling edge of band s-1 and the rising edge of band s, where s = seg(k) numbers the interval between two
-// consecutive band centres.  Segments are cut into pieces of at most 16 bins (an empty segment is one empty piece, so
-// that piece index == segment index whenever no segment is longer than 16 bins -- 128 mels: the kernel's fast path),
-// pieces are dealt to (slot, lane) by length, and every band gets the piece ranges of its rising segment (b) and of its
-// falling segment (b + 1).  Returns false (kernel not applicable) unless the table has exactly that structure.
-bool v2_build_segments(mst_plan* p, const float* fb, std::vector<float2>& segw, std::vector<int>& segstart,
-                       std::vector<int>& segid, std::vector<int2>& bandtab) {
-  const int M = p->n_mels, n_bins = p->n_fft / 2 + 1;
-  if (p->n_fft != 1024 || M > 256) return false;
-  std::vector<int> seg;
-  std::vector<float> wl, wh;
-  if (!segment_bins(fb, n_bins, M, seg, wl, wh)) return false;
-  const int nseg = M + 1;
-  std::vector<int> start(nseg, 0), len(nseg, 0);
-  for (int k = n_bins - 1; k >= 0; --k) start[seg[k]] = k, ++len[seg[k]];
-  struct Piece { int start, len; };
-  std::vector<Piece> pieces;
-  std::vector<int> first(nseg, 0), cnt(nseg, 0);
-  p->v2_maxcnt = 1;
-  for (int sg = 0; sg < nseg; ++sg) {
-    first[sg] = (int)pieces.size();
-    if (len[sg] == 0) pieces.push_back({0, 0}), cnt[sg] = 1;
-    for (int o = 0; o < len[sg]; o += 16) pieces.push_back({start[sg] + o, std::min(16, len[sg] - o)}), ++cnt[sg];
-    p->v2_maxcnt = std::max(p->v2_maxcnt, cnt[sg]);
-  }
-  const int np = (int)pieces.size();
-  if (np > v2::kExDump) return false;
-  std::vector<int> order(np);
-  for (int i = 0; i < np; ++i) order[i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pieces[a].len > pieces[b].len; });
-  p->v2_nslot = (np + 63) / 64;
-  if (p->v2_nslot > kV2Slots || (M <= 128 && p->v2_nslot > 3)) return false;
-  segstart.assign((size_t)p->v2_nslot * 64, 0);
-  segid.assign((size_t)p->v2_nslot * 64, v2::kExDump);
-  int off = 0;
-  for (int r = 0; r < p->v2_nslot; ++r) {
-    int gl = 0;
-    for (int lane = 0; lane < 64 && r * 64 + lane < np; ++lane) gl = std::max(gl, pieces[order[r * 64 + lane]].len);
-    p->v2_glen[r] = gl, p->v2_goff[r] = off;
-    segw.resize((size_t)(off + gl) * 64, make_float2(0.f, 0.f));
-    for (int lane = 0; lane < 64 && r * 64 + lane < np; ++lane) {
-      const int pc = order[r * 64 + lane];
-      segstart[(size_t)r * 64 + lane] = pieces[pc].start, segid[(size_t)r * 64 + lane] = pc;
-      for (int i = 0; i < pieces[pc].len; ++i)
-        segw[(size_t)(off + i) * 64 + lane] = make_float2(wl[pieces[pc].start + i], wh[pieces[pc].start + i]);
-    }
-    off += gl;
-  }
-  if (segw.size() & 1) segw.push_back(make_float2(0.f, 0.f));
-  if (segw.empty()) segw.resize(2, make_float2(0.f, 0.f));
-  p->v2_segw_count = (int)segw.size();
-  bandtab.assign(256, make_int2(v2::kExDump, v2::kExDump));
-  for (int b = 0; b < M; ++b)
-    bandtab[(size_t)(b >> 6) * 64 + (b & 63)] = make_int2(first[b] | (cnt[b] << 16), first[b + 1] | (cnt[b + 1] << 16));
-  return true;
 }
 
 // the piece table has the shape melfeat_v2_kernel<..., STD> hard-codes (the 128-mel HTK filterbank at 44.1 kHz / n_fft 1024)
 bool v2_table_is_standard(const mst_plan* p) {
-  return p->n_mels == 128 && p->v2_nslot == 3 && p->v2_maxcnt == 1 && p->v2_glen[0] == 14 && p->v2_glen[1] == 3 && p->v2_glen[2] == 0 &&
-         p->v2_goff[0] == 0 && p->v2_goff[1] == 14 && p->v2_goff[2] == 17;
+  const auto& t = p->sw;
+  return p->n_mels == 128 && t.nslot == 3 && t.maxcnt == 1 && t.glen[0] == 14 && t.glen[1] == 3 && !t.glen[2] && !t.goff[0] && t.goff[1] == 14 && t.goff[2] == 17;
 }
 
 }  // namespace
@@ -1301,134 +1186,52 @@ int mst_plan_create(mst_plan** out, int sample_rate, int n_fft, int hop, int n_m
   MST_REQUIRE(hop >= 1 && n_mels >= 4 && n_mels <= 256, "mst_plan_create: bad hop=%d / n_mels=%d", hop, n_mels);
   MST_REQUIRE(detailed_bins >= 0 && detailed_bins <= 256 && (detailed_bins == 0 || detailed_bins < n_mels ||
               detailed_bins == n_mels), "mst_plan_create: bad detailed_bins=%d", detailed_bins);
-  mst_plan* p = new mst_plan();
+  std::unique_ptr<mst_plan> p(new mst_plan());   // (a failed upload below frees what the plan already owns)
   p->sr = sample_rate, p->n_fft = n_fft, p->hop = hop, p->n_mels = n_mels, p->detailed_bins = detailed_bins;
   const int sd = detailed_bins > 0 ? detailed_bins + 2 : 5;
   p->feat_dim = 4 * (10 + sd) + 4;
-  p->nc = n_fft / 2;
-  p->nb = n_mels <= 128 ? 2 : 4;
-  const char* env = getenv("MST_MELFEAT_BATCHES");
-  p->batches_per_run = env ? std::max(1, atoi(env)) : 0;   // 0: chosen per launch (frames_per_run_of)
+  const StageAEnv env = read_stage_a_env();
+  p->batches_per_run = env.batches_per_run;
   const int n_bins = n_fft / 2 + 1;
+  auto& g = p->gen;
+  auto& sw = p->sw;
+  // sliding-window kernel, where the plan has one: the piece table and the packed-FFT twiddles
+  const bool v2 = n_fft == 1024 && hop == 256, v4 = n_fft == 2048 && hop == 512 && n_mels <= 128;
+  sw.wps = (env.v2_wps2 || n_mels > 128 || v4) ? 2 : 3;   // 4 bands per lane, and 2048 points, need the 256-register builds
+  stage_a::PieceTable t;
+  if (v2 || v4) t = stage_a::build_pieces(fb, n_bins, n_mels, v2 ? stage_a::v2_piece_opts(n_mels) : stage_a::v4_piece_opts());
+  sw.ok = t.ok, sw.nslot = t.nslot, sw.maxcnt = t.maxcnt, sw.segw_count = (int)t.segw.size();
+  for (int r = 0; r < kV2Slots; ++r) sw.glen[r] = t.glen[r], sw.goff[r] = t.goff[r];
+  const std::vector<int> bands = !t.ok ? std::vector<int>() : v2 ? stage_a::pack_bands16(t, n_mels, stage_a::kV2Dump) : stage_a::pack_bands8(t, n_mels);
+  std::vector<float2> t2(mstpk::kTw2Rows * 64), t3(mstpk::kTw3Rows * 64);
+  mstpk::fill_twiddles_host(t2.data(), t3.data());
+  const std::vector<stage_a::F2> t4 = v4 ? stage_a::tw4_twiddles() : std::vector<stage_a::F2>();
 
-  // sparse mel table: per band contiguous support [start, start+len)
-  std::vector<int> start(n_mels, 0), len(n_mels, 0);
-  for (int m = 0; m < n_mels; ++m) {
-    int lo = -1, hi = -1;
-    for (int k = 0; k < n_bins; ++k)
-      if (fb[(size_t)k * n_mels + m] != 0.0f) {
-        if (lo < 0) lo = k;
-        hi = k;
-      }
-    if (lo >= 0) start[m] = lo, len[m] = hi - lo + 1;
-  }
-  // lane -> bands: slot r even: r/2*128 + lane ; r odd: (r/2)*128 + 127 - lane  (pairs a narrow low band with a
-  // wide high band).  Weights go into a zero-padded table melw[goff[r] + i*64 + lane], i < glen[r] = the longest
-  // support in slot r, so the gather loop has a uniform trip count and no divergence.
-  std::vector<LaneBand> lbs((size_t)p->nb * 64);
-  std::vector<float> melw;
-  for (int r = 0; r < 4; ++r) p->glen[r] = p->goff[r] = 0;
-  for (int r = 0; r < p->nb; ++r) {
-    int gl = 0;
-    for (int lane = 0; lane < 64; ++lane) {
-      const int m = (r / 2) * 128 + ((r & 1) ? 127 - lane : lane);
-      lbs[(size_t)r * 64 + lane] = (m < n_mels) ? LaneBand{m, start[m]} : LaneBand{-1, 0};
-      if (m < n_mels) gl = std::max(gl, len[m]);
-    }
-    p->glen[r] = gl;
-    p->goff[r] = (int)melw.size();
-    melw.resize(melw.size() + (size_t)gl * 64, 0.f);
-    for (int lane = 0; lane < 64; ++lane) {
-      const int m = lbs[(size_t)r * 64 + lane].band;
-      if (m < 0) continue;
-      for (int i = 0; i < len[m]; ++i)
-        melw[(size_t)p->goff[r] + (size_t)i * 64 + lane] = fb[(size_t)(start[m] + i) * n_mels + m];
-    }
-  }
-  p->nnz = (int)melw.size();
-  if (melw.empty()) melw.push_back(0.f);
-  std::vector<float2> tw;
-  for (auto pr : passes_of(p->nc)) add_pass_tw(tw, p->nc, pr.first, pr.second);
-  p->tw_count = (int)tw.size();
-  std::vector<float2> tw2;
-  if (n_fft <= 1024)
-    for (auto pr : passes_of(n_fft)) add_pass_tw(tw2, n_fft, pr.first, pr.second);
-  p->tw2_count = (int)tw2.size();
-  if (tw2.empty()) tw2.push_back(make_float2(1.f, 0.f));
-  std::vector<float2> post(p->nc);
-  for (int q = 0; q < p->nc / 64; ++q)
-    for (int lane = 0; lane < 64; ++lane) {
-      const int k = lane + 64 * q;
-      const double a = -2.0 * M_PI * (double)k / (double)n_fft;
-      post[(size_t)q * 64 + lane] = make_float2((float)cos(a), (float)sin(a));
-    }
-  {   // sliding-window kernel tables (standard configuration only)
-    std::vector<float2> segw, t2(mstpk::kTw2Rows * 64), t3(mstpk::kTw3Rows * 64);
-    std::vector<int> segstart, segid;
-    std::vector<int2> bandtab;
-    const char* w = getenv("MST_V2_WPS");
-    p->v2_wps = ((w && atoi(w) == 2) || n_mels > 128) ? 2 : 3;   // 4 bands per lane need the 256-register build
-    p->v2_ok = n_fft == 1024 && hop == 256 && v2_build_segments(p, fb, segw, segstart, segid, bandtab);
-    if (p->v2_ok) {
-      mstpk::fill_twiddles_host(t2.data(), t3.data());
-      int rc2;
-      if ((rc2 = mst::upload(&p->d_v2_tw2, t2.data(), t2.size())) || (rc2 = mst::upload(&p->d_v2_tw3, t3.data(), t3.size())) ||
-          (rc2 = mst::upload(&p->d_v2_segw, segw.data(), segw.size())) ||
-          (rc2 = mst::upload(&p->d_v2_segstart, segstart.data(), segstart.size())) ||
-          (rc2 = mst::upload(&p->d_v2_segid, segid.data(), segid.size())) ||
-          (rc2 = mst::upload(&p->d_v2_bandtab, bandtab.data(), bandtab.size()))) {
-        mst_plan_destroy(p);
-        return rc2;
-      }
-    }
-  }
-  {   // n_fft 2048 / hop 512 variant
-    std::vector<float2> segw, t2(mstpk::kTw2Rows * 64), t3(mstpk::kTw3Rows * 64), t4(16 * 64);
-    std::vector<int> pstart, pid, bandtab;
-    p->v4_ok = n_fft == 2048 && hop == 512 && v4_build_pieces(p, fb, segw, pstart, pid, bandtab);
-    if (p->v4_ok) {
-      mstpk::fill_twiddles_host(t2.data(), t3.data());
-      for (int t = 0; t < 8; ++t)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int u = 0; u < 2; ++u) {
-            const int k = (u ? (lane ? 128 - lane : 64) : lane) + 128 * t;
-            const double a = -2.0 * M_PI * (double)k / 2048.0;
-            t4[(size_t)(8 * u + t) * 64 + lane] = make_float2((float)cos(a), (float)sin(a));
-          }
-      int rc2;
-      if ((rc2 = mst::upload(&p->d_v2_tw2, t2.data(), t2.size())) || (rc2 = mst::upload(&p->d_v2_tw3, t3.data(), t3.size())) ||
-          (rc2 = mst::upload(&p->d_v4_tw4, t4.data(), t4.size())) || (rc2 = mst::upload(&p->d_v4_segw, segw.data(), segw.size())) ||
-          (rc2 = mst::upload(&p->d_v4_pstart, pstart.data(), pstart.size())) ||
-          (rc2 = mst::upload(&p->d_v4_pid, pid.data(), pid.size())) ||
-          (rc2 = mst::upload(&p->d_v4_bandtab, bandtab.data(), bandtab.size()))) {
-        mst_plan_destroy(p);
-        return rc2;
-      }
-    }
-  }
+  // older kernels: the lane-band table and the wave-FFT twiddles
+  g.nb = n_mels <= 128 ? 2 : 4;
+  const stage_a::LaneBandTable lb = stage_a::build_lane_bands(fb, n_bins, n_mels, g.nb);
+  g.nnz = lb.nnz;
+  for (int r = 0; r < 4; ++r) g.glen[r] = lb.glen[r], g.goff[r] = lb.goff[r];
+  const std::vector<stage_a::F2> tw = stage_a::fft_twiddles(n_fft / 2), post = stage_a::post_twiddles(n_fft);
+  std::vector<stage_a::F2> tw2;
+  if (n_fft <= 1024) tw2 = stage_a::fft_twiddles(n_fft);
+  g.tw_count = (int)tw.size(), g.tw2_count = (int)tw2.size();
+  if (tw2.empty()) tw2.push_back(stage_a::F2{1.f, 0.f});
+  auto f2 = [](const std::vector<stage_a::F2>& v) { return reinterpret_cast<const float2*>(v.data()); };
   int rc;
-  if ((rc = mst::upload(&p->d_window, window, (size_t)n_fft)) || (rc = mst::upload(&p->d_tw, tw.data(), tw.size())) ||
-      (rc = mst::upload(&p->d_tw2, tw2.data(), tw2.size())) ||
-      (rc = mst::upload(&p->d_post, post.data(), post.size())) ||
-      (rc = mst::upload(&p->d_melw, melw.data(), melw.size())) ||
-      (rc = mst::upload(&p->d_lanebands, lbs.data(), lbs.size()))) {
-    mst_plan_destroy(p);
+  if ((t.ok && ((rc = sw.tw2.upload(t2.data(), t2.size())) || (rc = sw.tw3.upload(t3.data(), t3.size())) ||
+                (v4 && (rc = sw.tw4.upload(f2(t4), t4.size()))) || (rc = sw.segw.upload(f2(t.segw), t.segw.size())) ||
+                (rc = sw.start.upload(t.start.data(), t.start.size())) || (rc = sw.id.upload(t.id.data(), t.id.size())) ||
+                (rc = sw.bandtab.upload(bands.data(), bands.size())))) ||
+      (rc = p->window.upload(window, (size_t)n_fft)) || (rc = g.tw.upload(f2(tw), tw.size())) || (rc = g.tw2.upload(f2(tw2), tw2.size())) ||
+      (rc = g.post.upload(f2(post), post.size())) || (rc = g.melw.upload(lb.melw.data(), lb.melw.size())) ||
+      (rc = g.lanebands.upload(lb.lanebands.data(), lb.lanebands.size())))
     return rc;
-  }
-  *out = p;
+  *out = p.release();
   return MST_OK;
 }
 
-void mst_plan_destroy(mst_plan* p) {
-  if (!p) return;
-  (void)hipFree(p->d_window), (void)hipFree(p->d_tw), (void)hipFree(p->d_tw2), (void)hipFree(p->d_post), (void)hipFree(p->d_melw),
-      (void)hipFree(p->d_lanebands);
-  (void)hipFree(p->d_v2_tw2), (void)hipFree(p->d_v2_tw3), (void)hipFree(p->d_v2_segw), (void)hipFree(p->d_v2_segstart),
-      (void)hipFree(p->d_v2_segid), (void)hipFree(p->d_v2_bandtab);
-  (void)hipFree(p->d_v4_tw4), (void)hipFree(p->d_v4_segw), (void)hipFree(p->d_v4_pstart), (void)hipFree(p->d_v4_pid),
-      (void)hipFree(p->d_v4_bandtab);
-  delete p;
-}
+void mst_plan_destroy(mst_plan* p) { delete p; }
 
 int mst_plan_frames(const mst_plan* p, int T) { return p ? 1 + T / p->hop : MST_EINVAL; }
 int mst_plan_feature_dim(const mst_plan* p) { return p ? p->feat_dim : MST_EINVAL; }
@@ -1436,23 +1239,131 @@ int mst_plan_feature_dim(const mst_plan* p) { return p ? p->feat_dim : MST_EINVA
 size_t mst_melfeat_workspace_bytes(const mst_plan* p, int B, int T) {
   if (!p || B <= 0 || T <= 0) return 0;
   const int F = 1 + T / p->hop;
-  const int runs = std::max(runs_per_clip(p, B, F), p->v2_ok ? v2_runs(p, F) : (p->v4_ok ? v4_runs(F) : 0));
+  const int runs = std::max(runs_per_clip(p, F), p->sw.ok ? sw_runs(p, F) : 0);
   return mst::align_up((size_t)B * runs * pstride_of(p) * sizeof(float), 256);
 }
 
 }  // extern "C"
 
 namespace {
+
 struct LogmelOut {   // where and how the log-mel leaves stage A (mst.h: MST_LOGMEL_*)
   int layout = MST_LOGMEL_REF;
   void* lo = nullptr;          // MST_LOGMEL_CM16: low parts
   unsigned* absmax = nullptr;  // optional [B]
 };
-int melfeat_forward_impl(const mst_plan* p, const void* const stems4[4], bool pcm16, long long clip_stride, int B, int T,
-                         float* logmel, float* feats, void* workspace, size_t workspace_bytes, void* stream,
-                         const LogmelOut& lo = LogmelOut());
-bool plan_uses_v2(const mst_plan* p);
+
+// MST_STAGE_A=spw | generic selects the older kernels
+bool plan_uses_v2(const mst_plan* p) { return p->sw.ok && !read_stage_a_env().old_kernels; }
+
+// fn(float{}) or fn(short{}): the sample type of the waveform;  fn(integral_constant<n_fft>): the generic kernel's FFT length
+template <typename Fn>
+int with_sample_type(bool pcm16, Fn fn) { return pcm16 ? fn(short{}) : fn(float{}); }
+template <typename Fn>
+auto with_n_fft(int n_fft, Fn fn) {
+  if (n_fft == 512) return fn(std::integral_constant<int, 512>{});
+  if (n_fft == 1024) return fn(std::integral_constant<int, 1024>{});
+  return fn(std::integral_constant<int, 2048>{});
 }
+
+// The launch functions get their parameter struct with the common fields filled in.  K2Params or K4Params: the rest they share
+template <typename Params, typename Launch>
+int launch_sliding_window(const mst_plan* p, Params& k, const LogmelOut& lmo, bool pcm16, Launch launch) {
+  const auto& sw = p->sw;
+  k.out_mode = lmo.layout, k.logmel_lo = lmo.lo, k.absmax = lmo.absmax;
+  k.tw2 = sw.tw2.get(), k.tw3 = sw.tw3.get(), k.segw = sw.segw.get();
+  k.nslot = sw.nslot, k.segw_count = sw.segw_count, k.maxcnt = sw.maxcnt, k.fpw = sw_fpw(p, k.F);
+  for (size_t r = 0; r < std::size(k.glen); ++r) k.glen[r] = sw.glen[r], k.goff[r] = sw.goff[r];
+  return with_sample_type(pcm16, launch);
+}
+
+int launch_v2_2048(const mst_plan* p, K4Params k, const LogmelOut& lmo, bool pcm16, hipStream_t st) {
+  k.tw4 = p->sw.tw4.get(), k.pstart = p->sw.start.get(), k.pid = p->sw.id.get(), k.bandtab = p->sw.bandtab.get();
+  return launch_sliding_window(p, k, lmo, pcm16, [&](auto s) { return launch_melfeat_v2_2048<decltype(s)>(k, k.B * k.runs_per_clip, st); });
+}
+
+int launch_v2(const mst_plan* p, K2Params k, const LogmelOut& lmo, bool pcm16, bool no_std, hipStream_t st) {
+  k.segstart = p->sw.start.get(), k.segid = p->sw.id.get(), k.bandtab = reinterpret_cast<const int2*>(p->sw.bandtab.get());
+  const bool stdt = v2_table_is_standard(p) && !no_std;
+  return launch_sliding_window(p, k, lmo, pcm16, [&](auto s) {
+    using ST = decltype(s);
+    const int grid = k.B * k.runs_per_clip;
+    if (p->n_mels > 128) return launch_melfeat_v2<ST, 2, 4>(k, grid, st);   // 4 bands per lane, 4-frame blocks
+    return p->sw.wps == 3 ? launch_melfeat_v2<ST, 3>(k, grid, st, stdt) : launch_melfeat_v2<ST, 2>(k, grid, st);
+  });
+}
+
+size_t generic_lds_bytes(const mst_plan* p, int tile_bufs) {
+  return with_n_fft(p->n_fft, [&](auto N) { return GenericLds<N()>::bytes(p->gen.tw_count, p->gen.tw2_count, p->gen.nnz, p->n_mels, tile_bufs); });
+}
+
+// stem-per-wave-pair kernel for the standard configuration; the generic kernel covers everything else
+int launch_generic_or_spw(const mst_plan* p, KParams kp, bool pcm16, const StageAEnv& env, hipStream_t st) {
+  const auto& g = p->gen;
+  kp.tw = g.tw.get(), kp.tw2 = g.tw2.get(), kp.post = g.post.get(), kp.melw = g.melw.get(), kp.lanebands = g.lanebands.get();
+  kp.hop = p->hop, kp.tw_count = g.tw_count, kp.tw2_count = g.tw2_count, kp.nnz = g.nnz;
+  for (int r = 0; r < 4; ++r) kp.glen[r] = g.glen[r], kp.goff[r] = g.goff[r];
+  kp.frames_per_run = frames_per_run_of(p, kp.F);
+  bool base16 = true;
+  for (int i = 0; i < 4; ++i) base16 = base16 && (reinterpret_cast<uintptr_t>(kp.stem[i]) & 15) == 0;
+  kp.vec_ok = base16 && (kp.T % 2 == 0) && (p->hop % 2 == 0) && (kp.clip_stride % 2 == 0);
+  kp.vec4_ok = base16 && (kp.T % 4 == 0) && (p->hop % 4 == 0) && (kp.clip_stride % 4 == 0);
+  kp.tile_bufs = generic_lds_bytes(p, 2) <= kMaxLds ? 2 : 1;   // the output tile is double-buffered where the LDS allows
+  const int grid = kp.B * kp.runs_per_clip, n_fft = p->n_fft, M = p->n_mels;
+  const bool spw_ok = kp.vec_ok && kp.vec4_ok && p->hop * 4 == n_fft && M <= 128 && g.nb == 2 && (n_fft == 512 || n_fft == 1024) && !env.generic;
+  const bool spw3 = spw_ok && env.spw_wps == 3 && n_fft == 1024 && SpwLds<1024, 3>::bytes(g.tw2_count, g.nnz, M) <= kMaxLds;
+  const bool spw2 = spw_ok && !spw3 &&
+                    (n_fft == 1024 ? SpwLds<1024, 2>::bytes(g.tw2_count, g.nnz, M) : SpwLds<512, 2>::bytes(g.tw2_count, g.nnz, M)) <= kMaxLds;
+  return with_sample_type(pcm16, [&](auto s) {
+    using ST = decltype(s);
+    if (spw3) return launch_melfeat_spw<1024, ST, 3>(kp, grid, st);
+    if (spw2) return n_fft == 1024 ? launch_melfeat_spw<1024, ST, 2>(kp, grid, st) : launch_melfeat_spw<512, ST, 2>(kp, grid, st);
+    return with_n_fft(n_fft, [&](auto N) { return g.nb == 2 ? launch_melfeat<N(), 2, ST>(kp, grid, st) : launch_melfeat<N(), 4, ST>(kp, grid, st); });
+  });
+}
+
+int melfeat_forward_impl(const mst_plan* p, const void* const stems4[4], bool pcm16, long long clip_stride, int B, int T,
+                         float* logmel, float* feats, void* workspace, size_t workspace_bytes, void* stream, const LogmelOut& lmo = LogmelOut()) {
+  MST_REQUIRE(p && stems4[0] && stems4[1] && stems4[2] && stems4[3], "mst_melfeat_forward: NULL plan/stems");
+  MST_REQUIRE(clip_stride >= 2LL * T, "mst_melfeat_forward_stems: clip_stride %lld < 2*T", clip_stride);
+  MST_REQUIRE(B > 0 && T > p->n_fft / 2, "mst_melfeat_forward: need B>0 and T > n_fft/2 (reflect pad); B=%d T=%d", B, T);
+  MST_REQUIRE((long long)B * 8 * T < (1LL << 40), "mst_melfeat_forward: input too large");
+  const size_t need = mst_melfeat_workspace_bytes(p, B, T);
+  if (!workspace || workspace_bytes < need)
+    return mst::fail(MST_ENOMEM, "mst_melfeat_forward: workspace %zu B < required %zu B", workspace_bytes, need);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int F = 1 + T / p->hop;
+  // (a plan whose tables do not fit melfeat_kernel even with a single output tile is refused whichever kernel would run)
+  const size_t lds = generic_lds_bytes(p, generic_lds_bytes(p, 2) <= kMaxLds ? 2 : 1);
+  MST_REQUIRE(lds <= kMaxLds, "mst_melfeat_forward: LDS %zu B exceeds 160 KiB", lds);
+  const StageAEnv env = read_stage_a_env();
+  const bool use_sw = p->sw.ok && !env.old_kernels;
+  MST_REQUIRE(lmo.layout == MST_LOGMEL_REF || use_sw, "mst_melfeat_forward: channel-minor log-mel needs the sliding-window kernels");
+  if (lmo.absmax) {
+    MST_REQUIRE(lmo.layout != MST_LOGMEL_REF, "mst_melfeat_forward: absmax comes with the channel-minor layouts only");
+    MST_HIP_CHECK(hipMemsetAsync(lmo.absmax, 0, (size_t)B * sizeof(unsigned), st));
+  }
+  const int runs = use_sw ? sw_runs(p, F) : runs_per_clip(p, F);   // the finalise kernel walks the same partial records
+  auto common = [&](auto k) {   // the fields KParams, K2Params and K4Params share
+    for (int i = 0; i < 4; ++i) k.stem[i] = stems4[i];
+    k.clip_stride = clip_stride, k.logmel = logmel, k.partials = reinterpret_cast<float*>(workspace), k.window = p->window.get();
+    k.B = B, k.T = T, k.F = F, k.M = p->n_mels, k.runs_per_clip = runs, k.pstride = pstride_of(p);
+    return k;
+  };
+  const int rc = !use_sw            ? launch_generic_or_spw(p, common(KParams{}), pcm16, env, st)
+                 : p->n_fft == 2048 ? launch_v2_2048(p, common(K4Params{}), lmo, pcm16, st)
+                                    : launch_v2(p, common(K2Params{}), lmo, pcm16, env.v2_nostd, st);
+  if (rc) return rc;
+  if (feats) {
+    const FParams fp{reinterpret_cast<const float*>(workspace), feats, p->n_mels, F, T, runs, pstride_of(p), p->detailed_bins, p->feat_dim};
+    hipLaunchKernelGGL(melfeat_finalize_kernel, dim3(B), dim3(256), FinalizeLds::bytes(p->n_mels, p->detailed_bins), st, fp);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return mst::fail(MST_EHIP, "melfeat_finalize_kernel launch failed: %s", hipGetErrorString(e));
+  }
+  return MST_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1502,158 +1413,10 @@ int mst_melfeat_forward_io(const mst_plan* p, const mst_melfeat_io* io, int B, i
               "mst_melfeat_forward_io: channel-minor log-mel must be 16-byte aligned");
   MST_REQUIRE(io->layout != MST_LOGMEL_CM16 || !io->logmel_lo || (reinterpret_cast<uintptr_t>(io->logmel_lo) & 15) == 0,
               "mst_melfeat_forward_io: channel-minor log-mel must be 16-byte aligned");
-  LogmelOut lo;
-  lo.layout = io->layout, lo.lo = io->logmel_lo, lo.absmax = io->absmax;
+  const LogmelOut lo{io->layout, io->logmel_lo, io->absmax};
   const void* four[4] = {io->stems4[0], io->stems4[1], io->stems4[2], io->stems4[3]};
   return melfeat_forward_impl(p, four, io->pcm16 != 0, io->clip_stride, B, T, static_cast<float*>(io->logmel), io->feats, workspace,
                               workspace_bytes, stream, lo);
 }
 
 }  // extern "C"
-
-namespace {
-
-bool stage_a_env_old() {
-  const char* which = getenv("MST_STAGE_A");
-  return (which && (!strcmp(which, "spw") || !strcmp(which, "generic"))) || getenv("MST_MELFEAT_GENERIC");
-}
-bool plan_uses_v2(const mst_plan* p) { return (p->v2_ok || p->v4_ok) && !stage_a_env_old(); }
-
-int melfeat_forward_impl(const mst_plan* p, const void* const stems4[4], bool pcm16, long long clip_stride, int B, int T,
-                         float* logmel, float* feats, void* workspace, size_t workspace_bytes, void* stream, const LogmelOut& lmo) {
-  MST_REQUIRE(p && stems4[0] && stems4[1] && stems4[2] && stems4[3], "mst_melfeat_forward: NULL plan/stems");
-  MST_REQUIRE(clip_stride >= 2LL * T, "mst_melfeat_forward_stems: clip_stride %lld < 2*T", clip_stride);
-  MST_REQUIRE(B > 0 && T > p->n_fft / 2, "mst_melfeat_forward: need B>0 and T > n_fft/2 (reflect pad); B=%d T=%d", B, T);
-  MST_REQUIRE((long long)B * 8 * T < (1LL << 40), "mst_melfeat_forward: input too large");
-  const size_t need = mst_melfeat_workspace_bytes(p, B, T);
-  if (!workspace || workspace_bytes < need)
-    return mst::fail(MST_ENOMEM, "mst_melfeat_forward: workspace %zu B < required %zu B", workspace_bytes, need);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int F = 1 + T / p->hop;
-  KParams kp{};
-  for (int i = 0; i < 4; ++i) kp.stem[i] = stems4[i];
-  kp.clip_stride = clip_stride;
-  kp.logmel = logmel, kp.partials = reinterpret_cast<float*>(workspace);
-  kp.window = p->d_window, kp.tw = p->d_tw, kp.tw2 = p->d_tw2, kp.tw2_count = p->tw2_count, kp.post = p->d_post, kp.melw = p->d_melw, kp.lanebands = p->d_lanebands;
-  kp.B = B, kp.T = T, kp.F = F, kp.M = p->n_mels, kp.hop = p->hop;
-  kp.tw_count = p->tw_count, kp.nnz = p->nnz;
-  for (int r = 0; r < 4; ++r) kp.glen[r] = p->glen[r], kp.goff[r] = p->goff[r];
-  kp.frames_per_run = frames_per_run_of(p, B, F);
-  kp.runs_per_clip = runs_per_clip(p, B, F);
-  kp.pstride = pstride_of(p);
-  bool base16 = true;
-  for (int i = 0; i < 4; ++i) base16 = base16 && (reinterpret_cast<uintptr_t>(stems4[i]) & 15) == 0;
-  kp.vec_ok = base16 && (T % 2 == 0) && (p->hop % 2 == 0) && (clip_stride % 2 == 0);
-  kp.vec4_ok = base16 && (T % 4 == 0) && (p->hop % 4 == 0) && (clip_stride % 4 == 0);
-  const int nc = p->nc;
-  const int nf = nf_of(p->n_fft);
-  const bool pair = p->n_fft <= 1024;
-  size_t lds = (size_t)(nc + (pair ? p->tw2_count : p->tw_count + nc) + kWaves * nf * (nc + nc / 8)) * sizeof(float2) +
-               (size_t)(((p->nnz + 3) & ~3) + 2 * 2 * p->n_mels * kTileStride) * sizeof(float);
-  kp.tile_bufs = 2;
-  if (lds > 160 * 1024) {  // fall back to a single output tile
-    lds -= (size_t)2 * p->n_mels * kTileStride * sizeof(float);
-    kp.tile_bufs = 1;
-  }
-  // the reduction buffers alias the FFT scratch: kWaves*4*NB*64 + kWaves*12 floats must fit
-  const size_t red_need = (size_t)(kWaves * 4 * p->nb * 64 + kWaves * 12) * sizeof(float);
-  MST_REQUIRE(red_need <= (size_t)kWaves * nf * (nc + nc / 8) * sizeof(float2), "internal: reduction buffer");
-  MST_REQUIRE(lds <= 160 * 1024, "mst_melfeat_forward: LDS %zu B exceeds 160 KiB", lds);
-  hipError_t e = hipErrorInvalidValue;
-  // sliding-window kernel for the standard configuration (MST_STAGE_A=spw | generic selects the older kernels)
-  const bool use_v2 = p->v2_ok && !stage_a_env_old();
-  const bool use_v4 = p->v4_ok && !stage_a_env_old();
-  MST_REQUIRE(lmo.layout == MST_LOGMEL_REF || use_v2 || use_v4, "mst_melfeat_forward: channel-minor log-mel needs the sliding-window kernels");
-  if (lmo.absmax) {
-    MST_REQUIRE(lmo.layout != MST_LOGMEL_REF, "mst_melfeat_forward: absmax comes with the channel-minor layouts only");
-    MST_HIP_CHECK(hipMemsetAsync(lmo.absmax, 0, (size_t)B * sizeof(unsigned), st));
-  }
-  if (use_v4) {
-    K4Params k4{};
-    for (int i = 0; i < 4; ++i) k4.stem[i] = stems4[i];
-    k4.clip_stride = clip_stride, k4.logmel = logmel, k4.partials = reinterpret_cast<float*>(workspace);
-    k4.out_mode = lmo.layout, k4.logmel_lo = lmo.lo, k4.absmax = lmo.absmax;
-    k4.window = p->d_window, k4.tw2 = p->d_v2_tw2, k4.tw3 = p->d_v2_tw3, k4.tw4 = p->d_v4_tw4, k4.segw = p->d_v4_segw;
-    k4.pstart = p->d_v4_pstart, k4.pid = p->d_v4_pid, k4.bandtab = p->d_v4_bandtab;
-    k4.B = B, k4.T = T, k4.F = F, k4.M = p->n_mels;
-    k4.nslot = p->v4_nslot, k4.segw_count = p->v4_segw_count, k4.maxcnt = p->v4_maxcnt;
-    for (int r = 0; r < 4; ++r) k4.glen[r] = p->v4_glen[r], k4.goff[r] = p->v4_goff[r];
-    k4.fpw = v4_fpw(F), k4.runs_per_clip = v4_runs(F), k4.pstride = pstride_of(p);
-    kp.runs_per_clip = k4.runs_per_clip;
-    const size_t lds4 = (size_t)((mstpk::kTw2Rows + mstpk::kTw3Rows + 16) * 64 + p->v4_segw_count + 1024 + 8 * v4::kScr4) * sizeof(float2) +
-                        (size_t)v4::kWPS * v4::kBLK * 4 * 128 * sizeof(float) + 16;
-    MST_REQUIRE(lds4 <= 160 * 1024, "mst_melfeat_forward: LDS %zu B exceeds 160 KiB", lds4);
-    const int grid4 = B * k4.runs_per_clip;
-    e = pcm16 ? launch_melfeat_v2_2048<short>(k4, grid4, lds4, st) : launch_melfeat_v2_2048<float>(k4, grid4, lds4, st);
-  } else if (use_v2) {
-    K2Params k2{};
-    for (int i = 0; i < 4; ++i) k2.stem[i] = stems4[i];
-    k2.clip_stride = clip_stride, k2.logmel = logmel, k2.partials = reinterpret_cast<float*>(workspace);
-    k2.out_mode = lmo.layout, k2.logmel_lo = lmo.lo, k2.absmax = lmo.absmax;
-    k2.window = p->d_window, k2.tw2 = p->d_v2_tw2, k2.tw3 = p->d_v2_tw3, k2.segw = p->d_v2_segw;
-    k2.segstart = p->d_v2_segstart, k2.segid = p->d_v2_segid, k2.bandtab = p->d_v2_bandtab, k2.maxcnt = p->v2_maxcnt;
-    k2.B = B, k2.T = T, k2.F = F, k2.M = p->n_mels;
-    k2.nslot = p->v2_nslot, k2.segw_count = p->v2_segw_count;
-    for (int r = 0; r < kV2Slots; ++r) k2.glen[r] = p->v2_glen[r], k2.goff[r] = p->v2_goff[r];
-    k2.fpw = v2_fpw(p, F), k2.runs_per_clip = v2_runs(p, F), k2.pstride = pstride_of(p);
-    kp.runs_per_clip = k2.runs_per_clip;   // the finalise kernel walks the same records
-    const int wps = p->v2_wps;
-    const bool wide = p->n_mels > 128;   // 4 bands per lane, 4-frame blocks
-    const size_t lds2 = (size_t)((mstpk::kTw2Rows + mstpk::kTw3Rows) * 64 + p->v2_segw_count + 4 * wps * mstpk::kScr) * sizeof(float2) +
-                        (size_t)(wps * (wide ? 4 : (wps == 2 ? 8 : 4)) * 4 * (wide ? 256 : 128) + 1024) * sizeof(float) + 16;
-    MST_REQUIRE(lds2 <= 160 * 1024, "mst_melfeat_forward: LDS %zu B exceeds 160 KiB", lds2);
-    const int grid2 = B * k2.runs_per_clip;
-    if (wide) e = pcm16 ? launch_melfeat_v2<short, 2, 4>(k2, grid2, lds2, st) : launch_melfeat_v2<float, 2, 4>(k2, grid2, lds2, st);
-    else if (wps == 3) {
-      const bool stdt = v2_table_is_standard(p) && !getenv("MST_V2_NOSTD");
-      e = pcm16 ? launch_melfeat_v2<short, 3>(k2, grid2, lds2, st, stdt) : launch_melfeat_v2<float, 3>(k2, grid2, lds2, st, stdt);
-    }
-    else e = pcm16 ? launch_melfeat_v2<short, 2>(k2, grid2, lds2, st) : launch_melfeat_v2<float, 2>(k2, grid2, lds2, st);
-  } else {
-  const int grid = B * kp.runs_per_clip;
-  // stem-per-wave-pair kernel for the standard configuration; the generic kernel covers everything else
-  // stem-per-wave-pair kernel for the standard configuration; the generic kernel covers everything else
-  const int wps = getenv("MST_SPW_WPS") ? atoi(getenv("MST_SPW_WPS")) : 3;
-  auto spw_lds = [&](int w) {
-    return (size_t)(nc + p->tw2_count + 4 * w * (p->n_fft + p->n_fft / 8)) * sizeof(float2) +
-           (size_t)(((p->nnz + 3) & ~3) + (w == 2 ? 16 : 6) * (8 * p->n_mels + 1)) * sizeof(float);
-  };
-  const bool spw_ok = kp.vec_ok && kp.vec4_ok && p->hop * 4 == p->n_fft && p->n_mels <= 128 && p->nb == 2 &&
-                      (p->n_fft == 512 || p->n_fft == 1024) && !getenv("MST_MELFEAT_GENERIC");
-  const bool spw3 = spw_ok && wps == 3 && p->n_fft == 1024 && spw_lds(3) <= 160 * 1024;
-  const bool spw = spw3 || (spw_ok && spw_lds(2) <= 160 * 1024);
-  if (spw3) {
-    e = pcm16 ? launch_melfeat_spw<1024, short, 3>(kp, grid, spw_lds(3), st) : launch_melfeat_spw<1024, float, 3>(kp, grid, spw_lds(3), st);
-  } else if (spw) {
-    const size_t lds_spw = spw_lds(2);
-    if (p->n_fft == 1024)
-      e = pcm16 ? launch_melfeat_spw<1024, short, 2>(kp, grid, lds_spw, st) : launch_melfeat_spw<1024, float, 2>(kp, grid, lds_spw, st);
-    else
-      e = pcm16 ? launch_melfeat_spw<512, short, 2>(kp, grid, lds_spw, st) : launch_melfeat_spw<512, float, 2>(kp, grid, lds_spw, st);
-  } else {
-#define MST_CASE(NF)                                                                                          \
-  case NF:                                                                                                    \
-    if (pcm16) e = (p->nb == 2) ? launch_melfeat<NF, 2, short>(kp, grid, lds, st) : launch_melfeat<NF, 4, short>(kp, grid, lds, st); \
-    else e = (p->nb == 2) ? launch_melfeat<NF, 2, float>(kp, grid, lds, st) : launch_melfeat<NF, 4, float>(kp, grid, lds, st);       \
-    break;
-  switch (p->n_fft) {
-    MST_CASE(512)
-    MST_CASE(1024)
-    MST_CASE(2048)
-  }
-#undef MST_CASE
-  }
-  }
-  if (e != hipSuccess) return mst::fail(MST_EHIP, "melfeat_kernel launch failed: %s", hipGetErrorString(e));
-  if (feats) {
-    FParams fp{kp.partials, feats, p->n_mels, F, T, kp.runs_per_clip, kp.pstride, p->detailed_bins, p->feat_dim};
-    const size_t flds = (size_t)(4 * p->n_mels + kNumScalars + 24 + 4 * (p->detailed_bins > 0 ? p->detailed_bins : 0)) *
-                        sizeof(double);
-    hipLaunchKernelGGL(melfeat_finalize_kernel, dim3(B), dim3(256), flds, st, fp);
-    e = hipGetLastError();
-    if (e != hipSuccess) return mst::fail(MST_EHIP, "melfeat_finalize_kernel launch failed: %s", hipGetErrorString(e));
-  }
-  return MST_OK;
-}
-
-}  // namespace

@@ -63,6 +63,7 @@ constexpr int kExDump = kExN - 1;
 constexpr int kExHi = 544;      // v2f rising-edge sums per piece
 constexpr int kExLo = kExHi + kExN;
 static_assert(kExLo + kExN <= kScr, "exchange areas must fit the FFT scratch");
+static_assert(kExDump == stage_a::kV2Dump && kV2Slots == stage_a::kMaxSlots, "the piece table is built for these limits");
 
 // |A|^2 and |s B|^2 (times 4) of bin k from Z[k] and Z[N-k]:  Z[k] + Z[N-k] = (2 Re A, 2 Re sB),
 // Z[k] - Z[N-k] = (-2 Im sB, 2 Im A)
@@ -201,6 +202,20 @@ template <int WPS> struct V2Geom {
   static constexpr bool MIX_EARLY = WPS == 2;  // mixture loads issued before the FFT (8 registers across it)
 };
 
+// LDS of melfeat_v2_kernel<., WPS, NBL, ..>; a_*: from the end of segw[segw_count]
+template <int WPS, int NBL>
+struct V2Lds {
+  static constexpr int BLK = NBL == 2 ? V2Geom<WPS>::BLK : 4, MB = 64 * NBL, WAVES = 4 * WPS;
+  // v2f tw2[7 * 64], tw3[14 * 64], segw[segw_count] (even)
+  static constexpr int tw2 = 0, tw3 = tw2 + mstpk::kTw2Rows * 64 * 8, segw = tw3 + mstpk::kTw3Rows * 64 * 8;
+  // float win[1024] (only when the window does not live in registers), exch[WPS][BLK frames][4 stems][MB]
+  static constexpr int a_win = 0, a_exch = a_win + (V2Geom<WPS>::WIN_LDS ? 1024 * 4 : 0);
+  // v2f scr[WAVES][kScr] (FFT scratch, piece sums, channel-minor staging, final reduction); unsigned amax, padded to 16 bytes
+  static constexpr int a_scr = a_exch + WPS * BLK * 4 * MB * 4, a_amax = a_scr + WAVES * mstpk::kScr * 8;
+  static constexpr size_t bytes(int segw_count) { return (size_t)segw + (size_t)segw_count * 8 + a_amax + 16; }
+  static_assert(WAVES * NBL * 64 + WAVES * 16 <= 2 * WAVES * mstpk::kScr, "the reduction buffer must fit the FFT scratch");
+};
+
 // NBL = bands per lane: 2 (n_mels <= 128) or 4 (n_mels <= 256, BASELINE configs[4]; two waves per SIMD only).
 // CM: the channel-minor output build (out_mode 1 or 2, optional absmax); false: the reference layout (out_mode 0) -- two
 // builds because the 168-register budget of three waves per SIMD holds either store path, not both.
@@ -216,19 +231,21 @@ __global__ __launch_bounds__(WPS * 256) void melfeat_v2_kernel(const K2Params p)
 #pragma clang fp contract(off)
   using namespace mstpk;
   using namespace v2;
-  constexpr int kWaves = 4 * WPS, kThreads = kWaves * 64, BLK = NBL == 2 ? V2Geom<WPS>::BLK : 4, MB = 64 * NBL;
+  using L = V2Lds<WPS, NBL>;
+  constexpr int kWaves = L::WAVES, kThreads = kWaves * 64, BLK = L::BLK, MB = L::MB;
   constexpr bool kUnrollBlock = STD && BLK == 4;   // the standard-table build walks its 4-frame blocks unrolled (melfeat_v2_frame.inc)
   constexpr bool WIN_LDS = V2Geom<WPS>::WIN_LDS, MIX_EARLY = V2Geom<WPS>::MIX_EARLY;
   constexpr int SB = BLK;
   constexpr float kLn2 = 0.69314718055994530942f;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  v2f* s_tw2 = reinterpret_cast<v2f*>(smem);                      // [7 * 64]
-  v2f* s_tw3 = s_tw2 + kTw2Rows * 64;                             // [14 * 64]
-  v2f* s_segw = s_tw3 + kTw3Rows * 64;                            // [segw_count] (even)
-  float* s_win = reinterpret_cast<float*>(s_segw + p.segw_count);   // [1024] (only when the window does not live in registers)
-  float* s_exch = s_win + (WIN_LDS ? 1024 : 0);                     // [WPS][BLK frames][4 stems][MB]
-  v2f* s_scr = reinterpret_cast<v2f*>(s_exch + WPS * BLK * 4 * MB);   // [kWaves][kScr]
-  unsigned* s_amax = reinterpret_cast<unsigned*>(s_scr + kWaves * kScr);   // max |log-mel| of this workgroup's frames (float bits)
+  v2f* s_tw2 = reinterpret_cast<v2f*>(smem + L::tw2);
+  v2f* s_tw3 = reinterpret_cast<v2f*>(smem + L::tw3);
+  v2f* s_segw = reinterpret_cast<v2f*>(smem + L::segw);
+  unsigned char* after_segw = reinterpret_cast<unsigned char*>(s_segw + p.segw_count);
+  float* s_win = reinterpret_cast<float*>(after_segw + L::a_win);
+  float* s_exch = reinterpret_cast<float*>(after_segw + L::a_exch);
+  v2f* s_scr = reinterpret_cast<v2f*>(after_segw + L::a_scr);
+  unsigned* s_amax = reinterpret_cast<unsigned*>(after_segw + L::a_amax);
   static_assert(!STD || NBL == 2, "the standard table has 128 bands");
   const int M = STD ? 128 : p.M, T = p.T;
   const int nslot = STD ? 3 : p.nslot, maxcnt = STD ? 1 : p.maxcnt;
@@ -487,15 +504,12 @@ __global__ __launch_bounds__(WPS * 256) void melfeat_v2_kernel(const K2Params p)
   }
 }
 
-template <typename ST, int WPS, int NBL, bool CM, bool STD = false>
-hipError_t launch_melfeat_v2_cm(const K2Params& kp, int grid, size_t lds, hipStream_t st) {
-  return mst::launch_lds<melfeat_v2_kernel<ST, WPS, NBL, CM, STD>>(dim3(grid), dim3(WPS * 256), lds, st, kp);
-}
 // std_table: the plan's piece table has the standard shape (see STD above); used by the channel-minor builds of the 12-wave kernel
 template <typename ST, int WPS, int NBL = 2>
-hipError_t launch_melfeat_v2(const K2Params& kp, int grid, size_t lds, hipStream_t st, bool std_table = false) {
+int launch_melfeat_v2(const K2Params& kp, int grid, hipStream_t st, bool std_table = false) {
+  const size_t lds = V2Lds<WPS, NBL>::bytes(kp.segw_count);
   if constexpr (WPS == 3 && NBL == 2)
-    if (std_table && kp.out_mode != 0) return launch_melfeat_v2_cm<ST, WPS, NBL, true, true>(kp, grid, lds, st);
-  return kp.out_mode != 0 ? launch_melfeat_v2_cm<ST, WPS, NBL, true>(kp, grid, lds, st)
-                          : launch_melfeat_v2_cm<ST, WPS, NBL, false>(kp, grid, lds, st);
+    if (std_table && kp.out_mode != 0) return launch_stage_a<melfeat_v2_kernel<ST, WPS, NBL, true, true>>(kp, grid, WPS * 256, lds, st);
+  return kp.out_mode != 0 ? launch_stage_a<melfeat_v2_kernel<ST, WPS, NBL, true>>(kp, grid, WPS * 256, lds, st)
+                          : launch_stage_a<melfeat_v2_kernel<ST, WPS, NBL, false>>(kp, grid, WPS * 256, lds, st);
 }

@@ -41,24 +41,39 @@ constexpr int kScr4 = 1328;      // float2 per wave: FFT scratch (1152) / P2[102
 constexpr int kEx4Hi = 1056;     // rising-edge sums per piece [136]
 constexpr int kEx4Lo = 1192;     // falling-edge sums per piece [136]
 constexpr int kWPS = 2, kBLK = 4;
+constexpr int kEx4N = stage_a::kV4Dump + 1;   // entries per piece-sum array; the last one is the dump slot of unused lanes
+static_assert(kEx4N == 136 && kEx4Hi + kEx4N <= kEx4Lo && kEx4Lo + kEx4N <= kScr4, "exchange areas must fit the FFT scratch");
 }  // namespace v4
+
+// LDS of melfeat_v2_2048_kernel; a_*: from the end of segw[segw_count]
+struct V4Lds {
+  static constexpr int WAVES = 4 * v4::kWPS;
+  // v2f tw2[7 * 64], tw3[14 * 64], tw4[16 * 64], segw[segw_count] (even)
+  static constexpr int tw2 = 0, tw3 = tw2 + mstpk::kTw2Rows * 64 * 8, tw4 = tw3 + mstpk::kTw3Rows * 64 * 8, segw = tw4 + 16 * 64 * 8;
+  // v2f win[1024] pairs (w[2m], w[2m+1]); float exch[WPS][BLK frames][4 stems][128]; v2f scr[WAVES][kScr4]; unsigned amax, padded to 16 bytes
+  static constexpr int a_win = 0, a_exch = a_win + 1024 * 8, a_scr = a_exch + v4::kWPS * v4::kBLK * 4 * 128 * 4, a_amax = a_scr + WAVES * v4::kScr4 * 8;
+  static constexpr size_t bytes(int segw_count) { return (size_t)segw + (size_t)segw_count * 8 + a_amax + 16; }
+  static_assert(WAVES * 2 * 64 + WAVES * 16 <= 2 * WAVES * v4::kScr4, "the reduction buffer must fit the FFT scratch");
+};
 
 template <typename ST, bool CM = false>   // CM: channel-minor output build (melfeat_v2.inc)
 __global__ __launch_bounds__(512) void melfeat_v2_2048_kernel(const K4Params p) {
   using namespace mstpk;
   using namespace v2;
   using namespace v4;
-  constexpr int WPS = kWPS, BLK = kBLK, kWaves = 4 * WPS, kThreads = kWaves * 64;
+  using L = V4Lds;
+  constexpr int WPS = kWPS, BLK = kBLK, kWaves = L::WAVES, kThreads = kWaves * 64;
   constexpr float kLn2 = 0.69314718055994530942f;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  v2f* s_tw2 = reinterpret_cast<v2f*>(smem);                          // [7 * 64]
-  v2f* s_tw3 = s_tw2 + kTw2Rows * 64;                                 // [14 * 64]
-  v2f* s_tw4 = s_tw3 + kTw3Rows * 64;                                 // [16 * 64]
-  v2f* s_segw = s_tw4 + 16 * 64;                                      // [segw_count] (even)
-  v2f* s_win = s_segw + p.segw_count;                                 // [1024] pairs (w[2m], w[2m+1])
-  float* s_exch = reinterpret_cast<float*>(s_win + 1024);             // [WPS][BLK frames][4 stems][128]
-  v2f* s_scr = reinterpret_cast<v2f*>(s_exch + WPS * BLK * 4 * 128);  // [kWaves][kScr4]
-  unsigned* s_amax = reinterpret_cast<unsigned*>(s_scr + kWaves * kScr4);   // max |log-mel| of this workgroup's frames (float bits)
+  v2f* s_tw2 = reinterpret_cast<v2f*>(smem + L::tw2);
+  v2f* s_tw3 = reinterpret_cast<v2f*>(smem + L::tw3);
+  v2f* s_tw4 = reinterpret_cast<v2f*>(smem + L::tw4);
+  v2f* s_segw = reinterpret_cast<v2f*>(smem + L::segw);
+  unsigned char* after_segw = reinterpret_cast<unsigned char*>(s_segw + p.segw_count);
+  v2f* s_win = reinterpret_cast<v2f*>(after_segw + L::a_win);
+  float* s_exch = reinterpret_cast<float*>(after_segw + L::a_exch);
+  v2f* s_scr = reinterpret_cast<v2f*>(after_segw + L::a_scr);
+  unsigned* s_amax = reinterpret_cast<unsigned*>(after_segw + L::a_amax);
   const int M = p.M, T = p.T;
   constexpr bool cm = CM;
 
@@ -437,11 +452,9 @@ __global__ __launch_bounds__(512) void melfeat_v2_2048_kernel(const K4Params p) 
   }
 }
 
-template <typename ST, bool CM>
-hipError_t launch_melfeat_v2_2048_cm(const K4Params& kp, int grid, size_t lds, hipStream_t st) {
-  return mst::launch_lds<melfeat_v2_2048_kernel<ST, CM>>(dim3(grid), dim3(512), lds, st, kp);
-}
 template <typename ST>
-hipError_t launch_melfeat_v2_2048(const K4Params& kp, int grid, size_t lds, hipStream_t st) {
-  return kp.out_mode != 0 ? launch_melfeat_v2_2048_cm<ST, true>(kp, grid, lds, st) : launch_melfeat_v2_2048_cm<ST, false>(kp, grid, lds, st);
+int launch_melfeat_v2_2048(const K4Params& kp, int grid, hipStream_t st) {
+  const size_t lds = V4Lds::bytes(kp.segw_count);
+  return kp.out_mode != 0 ? launch_stage_a<melfeat_v2_2048_kernel<ST, true>>(kp, grid, 512, lds, st)
+                          : launch_stage_a<melfeat_v2_2048_kernel<ST, false>>(kp, grid, 512, lds, st);
 }

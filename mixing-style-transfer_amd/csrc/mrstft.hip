@@ -39,6 +39,7 @@ constexpr int kChunksPerBlock = 64;
 constexpr int kFwdMaxBlocks = 2048;   // DetAcc takes up to 2^14 contributions
 constexpr int kMaxRes = 16;
 constexpr int kBorder = 1024;         // floats per border and row (n_fft / 2 at most)
+constexpr int kMelMax = 256, kMelRounds = kMelMax / 64;   // log-mel backward: one lane per mel, kMelRounds mels per lane
 
 template <int N>
 struct Geo {
@@ -46,6 +47,12 @@ struct Geo {
   static constexpr int NF = N / NC, NCR = NC / 64, REGS = N / 64, SCR = N + N / 8, TW = FftPlan<NC>::TW;
   static constexpr int TWD = N == 2048 ? 1024 : 0, NB = N / 128 + 1;
   static constexpr size_t kLds = (size_t)(TW + TWD) * 8 + (size_t)N * 4 + (size_t)kWaves * SCR * 8;
+  // The backward kernels keep more behind kLds, in floats from Lds::acc: the overlap-add ring of kRound + R - 1 hop-sized
+  // chunks, and behind the ring (log-mel backward only) the waves' wv[2][kMelMax] and the cotangent tile gt[n_mels][wstride].
+  static constexpr int ring(int R, int hop) { return (kRound + R - 1) * hop; }
+  static constexpr int kWv = 0, kGt = kWv + 2 * kWaves * kMelMax;
+  static constexpr size_t bwd_lds(int R, int hop) { return kLds + (size_t)ring(R, hop) * 4; }
+  static constexpr size_t logmel_bwd_lds(int R, int hop, int n_mels, int wstride) { return bwd_lds(R, hop) + ((size_t)kGt + (size_t)n_mels * wstride) * 4; }
 };
 
 // element a lane holds in register r before the first pass / after the last pass
@@ -254,7 +261,7 @@ __global__ __launch_bounds__(kThreads) void mrstft_bwd_kernel(const BwdParams p)
   Lds<N> l(smem, wave);
   l.fill(p.window, tid);
   const int hop = p.hop, lh = p.lh, R = p.R, nslot = kRound + R - 1;
-  for (int i = tid; i < nslot * hop; i += kThreads) l.acc[i] = 0.f;
+  for (int i = tid; i < G::ring(R, hop); i += kThreads) l.acc[i] = 0.f;
   const int row = blockIdx.x / p.blocks_per_row, blk = blockIdx.x % p.blocks_per_row;
   const int c0 = blk * kChunksPerBlock, c1 = min(c0 + kChunksPerBlock, p.nchunks);
   const int fa = max(0, c0 - R + 1), fb = min(p.F - 1, c1 - 1);
@@ -371,8 +378,7 @@ hipError_t launch_fwd(const FwdParams& p, int grid, hipStream_t st) {
 }
 template <int N>
 hipError_t launch_bwd(const BwdParams& p, int grid, hipStream_t st) {
-  const size_t lds = Geo<N>::kLds + (size_t)(kRound + p.R - 1) * p.hop * sizeof(float);
-  return mst::launch_lds<mrstft_bwd_kernel<N>>(dim3(grid), dim3(kThreads), lds, st, p);
+  return mst::launch_lds<mrstft_bwd_kernel<N>>(dim3(grid), dim3(kThreads), Geo<N>::bwd_lds(p.R, p.hop), st, p);
 }
 
 size_t acc_bytes(int n_res) { return mst::align_up((size_t)3 * n_res * sizeof(mst::DetAcc), 256); }
@@ -469,8 +475,6 @@ namespace {
 constexpr int kBandMax = MST_LOGMEL_BAND_MAX;   // mel weights per bin the kernel carries
 constexpr size_t kMaxLds = 160 * 1024;
 
-constexpr int kMelMax = 256, kMelRounds = kMelMax / 64;   // one lane per mel, kMelRounds mels per lane
-
 struct LogmelBwdParams {
   const float* x;        // [rows][T]
   const float* g;        // [rows][n_mels][F] cotangent on the log-mel
@@ -492,9 +496,10 @@ __global__ __launch_bounds__(kThreads) void logmel_bwd_kernel(const LogmelBwdPar
   Lds<N> l(smem, wave);
   l.fill(p.window, tid);
   const int hop = p.hop, lh = p.lh, R = p.R, nslot = kRound + R - 1;
-  for (int i = tid; i < nslot * hop; i += kThreads) l.acc[i] = 0.f;
-  float2* wv = reinterpret_cast<float2*>(l.acc + nslot * hop) + wave * kMelMax;   // this wave's w = g / (mel + 1e-10), frames (A, B)
-  float* gt = l.acc + nslot * hop + 2 * kWaves * kMelMax;   // cotangent tile of this workgroup's frames, [n_mels][wstride]
+  for (int i = tid; i < G::ring(R, hop); i += kThreads) l.acc[i] = 0.f;
+  float* behind = l.acc + G::ring(R, hop);
+  float2* wv = reinterpret_cast<float2*>(behind + G::kWv) + wave * kMelMax;   // this wave's w = g / (mel + 1e-10), frames (A, B)
+  float* gt = behind + G::kGt;   // cotangent tile of this workgroup's frames, [n_mels][wstride]
   float4* Q = reinterpret_cast<float4*>(l.scr);   // per bin (w0 P_A, w0 P_B, w1 P_A, w1 P_B): the power spectrum times its two mel weights
   const int row = blockIdx.x / p.blocks_per_row, blk = blockIdx.x % p.blocks_per_row;
   const int c0 = blk * p.cpb, c1 = min(c0 + p.cpb, p.nchunks);
@@ -630,20 +635,19 @@ __global__ __launch_bounds__(kThreads) void logmel_bwd_kernel(const LogmelBwdPar
   }
 }
 
-template <int N>
-size_t logmel_bwd_lds(int R, int hop, int n_mels, int cpb) {
-  return Geo<N>::kLds + ((size_t)(kRound + R - 1) * hop + 2 * kWaves * kMelMax + (size_t)n_mels * ((cpb + R - 1) | 1)) * sizeof(float);
-}
+// row pitch of the cotangent tile: the cpb + R - 1 frames a workgroup reads, made odd
+int wstride_of(int cpb, int R) { return (cpb + R - 1) | 1; }
 
 template <int N>
 int launch_logmel_bwd(LogmelBwdParams& p, hipStream_t st) {
   // a workgroup owns 64 hop-sized chunks; fewer where the cotangent tile of 64 + R - 1 frames would not fit the CU's LDS next to
   // the transform's tables (n_fft = 2048 with more than ~118 mels)
   p.cpb = kChunksPerBlock;
-  while (p.cpb > 8 && logmel_bwd_lds<N>(p.R, p.hop, p.n_mels, p.cpb) > kMaxLds) p.cpb /= 2;
-  const size_t lds = logmel_bwd_lds<N>(p.R, p.hop, p.n_mels, p.cpb);
+  auto lds_of = [&](int cpb) { return Geo<N>::logmel_bwd_lds(p.R, p.hop, p.n_mels, wstride_of(cpb, p.R)); };
+  while (p.cpb > 8 && lds_of(p.cpb) > kMaxLds) p.cpb /= 2;
+  const size_t lds = lds_of(p.cpb);
   MST_REQUIRE(lds <= kMaxLds, "mst_logmel_backward: LDS %zu B exceeds 160 KiB (n_fft=%d hop=%d n_mels=%d)", lds, N, p.hop, p.n_mels);
-  p.wstride = (p.cpb + p.R - 1) | 1;
+  p.wstride = wstride_of(p.cpb, p.R);
   p.blocks_per_row = (p.nchunks + p.cpb - 1) / p.cpb;
   const long long grid = (long long)p.rows * p.blocks_per_row;
   MST_REQUIRE(grid < (1LL << 31), "mst_logmel_backward: %lld workgroups", grid);
