@@ -124,11 +124,13 @@ class TwoTimesRule:
     within 2 * e_ref (the rule of the log-mel and real-music tests), and norm-wise within 1e-4."""
 
     def __init__(self, case, report=True):
-        self.case, self.rows, self.report = case, [], report   # report: rows in the parity table of the GPU log
+        # report: rows in the parity table of the GPU log; "summary": the case's e_ref / worst line only (a sweep with
+        # dozens of quantities per case)
+        self.case, self.rows, self.report = case, [], report
 
     def add(self, name, got, ref32, ref64):
         import parity
-        if self.report:
+        if self.report is True:
             parity.record(f"tcn {self.case} {name} [ref fp32 vs f64]", ref32, ref64)
             parity.record(f"tcn {self.case} {name} [hip vs f64]", got, ref64)
         self.rows.append((name, max_rel(ref32, ref64)[0], *max_rel(got, ref64)))

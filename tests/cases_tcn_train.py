@@ -25,6 +25,9 @@ CASES = {
     "t_plain40": dict(H=40, nb=4, K=5, causal=False, film=False, B=2, T=1999),   # padded channels, activation after the sum
     "t_wide128": dict(H=128, nb=3, K=15, causal=False, film=True, B=1, T=1500),  # the split-channel instantiation
     "t_h8": dict(H=8, nb=4, K=15, causal=False, film=False, B=1, T=2000),        # H below one tile, B = 1
+    # odd tile counts (the second half of the output channels has one tile fewer) and idle threads in the row reductions
+    "t_odd72": dict(H=72, nb=3, K=7, causal=False, film=True, B=2, T=1201),      # HP = 80: 3 slots, 16 idle threads
+    "t_w100": dict(H=100, nb=2, K=4, causal=True, film=False, B=2, T=1100),      # HP = 112: 2 slots, 32 idle, 12 padded channels
 }
 FILM_KEYS = ("gamma1", "beta1", "gamma2", "beta2")
 # quantity groups of the parity rule (block conv biases are not among them: their gradient is mathematically zero)

@@ -1,6 +1,8 @@
 """Writes tests/golden/tcn_train_<case>.npz from the UNMODIFIED reference (its `src/tcn_mixer.py`) in train() mode.
 
-    python tests/golden/make_golden_tcn_train.py [REFERENCE_SRC]     # default: the directory make_golden.py reads
+    python tests/golden/make_golden_tcn_train.py [REFERENCE_SRC] [--cases NAME ...]
+                                                  # REFERENCE_SRC default: the directory make_golden.py reads
+                                                  # --cases: write these fixtures only (default: all of them)
 
 Runs only where the reference checkout exists; the tests read the fixtures, never the reference.  Per case
 (tests/cases_tcn_train.CASES) one forward + backward of loss = sum(y * dy) in fp32 and in float64.  The fp32 run notes the
@@ -30,9 +32,16 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
+def arguments():
+    """([REFERENCE_SRC], [case names after --cases])."""
+    args = sys.argv[1:]
+    at = args.index("--cases") if "--cases" in args else len(args)
+    return args[:at], args[at + 1:]
+
+
 def reference_src():
-    if len(sys.argv) > 1:
-        return sys.argv[1]
+    if arguments()[0]:
+        return arguments()[0][0]
     import re
     text = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "make_golden.py")).read()
     return re.search(r'sys\.path\.insert\(0, "([^"]*/src)"\)', text).group(1)
@@ -60,7 +69,12 @@ def run(c, dtype, namespace):
 
 def main():
     torch.set_num_threads(min(16, os.cpu_count() or 1))
-    for name, c in ctt.CASES.items():
+    names = arguments()[1] or list(ctt.CASES)
+    unknown = [n for n in names if n not in ctt.CASES]
+    if unknown:
+        sys.exit(f"no such case: {unknown}; cases: {list(ctt.CASES)}")
+    for name in names:
+        c = ctt.CASES[name]
         t0 = time.time()
         rec = ctt.Recorder()
         r32 = run(c, torch.float32, rec)

@@ -15,6 +15,7 @@ import torch
 
 import cases
 import cases_tcn as ct
+import cases_tcn_train as ctt
 import parity
 from mst_amd import _lib
 from mst_amd import tcn_mixer as tm
@@ -23,13 +24,14 @@ pytestmark = pytest.mark.gpu
 FILM_KEYS = ("gamma1", "beta1", "gamma2", "beta2")
 
 
-def build(c, E=ct.EMBED, dtype=torch.float32, device="cuda", backend="hip"):
+def build(c, E=ct.EMBED, dtype=torch.float32, device="cuda", backend="hip", sd=None, generator=True):
+    """The mixer with the seeded state dict (or `sd`) and, for a FiLM mixer unless `generator` is False, its generator."""
     tcn = tm.TCNMixer(**ct.mixer_kwargs(c))
-    tcn.load_state_dict(ct.make_tcn_state_dict(c), strict=True)
+    tcn.load_state_dict(sd if sd is not None else ct.make_tcn_state_dict(c), strict=True)
     tcn = tcn.to(device=device, dtype=dtype).eval()
     tcn.backend = backend
     gen = None
-    if c["film"]:
+    if c["film"] and generator:
         gen = tm.TCNFiLMGenerator(embed_dim=E, num_blocks=c["nb"], hidden_channels=c["H"])
         gen.load_state_dict(ct.make_film_state_dict(E, c), strict=True)
         gen = gen.to(device=device, dtype=dtype).eval()
@@ -37,24 +39,32 @@ def build(c, E=ct.EMBED, dtype=torch.float32, device="cuda", backend="hip"):
     return tcn, gen
 
 
-def hip_forward(c, x, E=ct.EMBED, taps=()):
-    """y, film (B, nb, 4, H) or None, hidden taps -- all on the kernels."""
-    tcn, gen = build(c, E)
+def hip_forward(c, x, E=ct.EMBED, taps=(), film=None, sd=None):
+    """y, film (B, nb, 4, H) or None, hidden taps -- all on the kernels.  `film`: the FiLM tensor itself instead of the
+    generator's; `sd`: a state dict instead of the seeded one."""
+    tcn, gen = build(c, E, sd=sd, generator=film is None)
     with torch.no_grad():
-        film = gen.film_tensor(ct.embeddings(x.shape[0], E).cuda()) if gen is not None else None
+        if gen is not None:
+            film = gen.film_tensor(ct.embeddings(x.shape[0], E).cuda())
+        elif film is not None:
+            film = film.cuda().contiguous()
         y, hs = tcn._forward_hip(x.cuda(), film, tuple(taps))
     torch.cuda.synchronize()
     return y.cpu(), None if film is None else film.cpu(), [h.cpu() for h in hs]
 
 
-def torch_forward(c, x, dtype, E=ct.EMBED, taps=()):
+def torch_forward(c, x, dtype, E=ct.EMBED, taps=(), film=None, sd=None):
     """The same on the torch tree on the host CPUs."""
-    tcn, gen = build(c, E, dtype, "cpu", "torch")
+    tcn, gen = build(c, E, dtype, "cpu", "torch", sd=sd, generator=film is None)
     got = {k: None for k in taps}
     with torch.no_grad():
-        params = gen(ct.embeddings(x.shape[0], E).to(dtype)) if gen is not None else None
+        params = None
+        if gen is not None:
+            params = gen(ct.embeddings(x.shape[0], E).to(dtype))
+        elif film is not None:
+            params = ctt.film_dicts(film.to(dtype))
         y = tcn._forward_torch(x.to(dtype), params, got)
-    film = None if gen is None else torch.stack([torch.stack([p[k] for k in FILM_KEYS], 1) for p in params], 1)
+    film = None if params is None else torch.stack([torch.stack([p[k] for k in FILM_KEYS], 1) for p in params], 1)
     return y, film, [got[k] for k in taps]
 
 

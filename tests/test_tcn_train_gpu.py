@@ -172,10 +172,14 @@ def _ws(h, B, T):
 
 @pytest.mark.parametrize("H,K,causal,T,block", [
     (8, 15, False, 1, 0), (16, 15, False, 37, 2), (16, 15, False, 37, 6), (40, 5, False, 2049, 1), (128, 15, False, 2049, 3),
-    (16, 4, True, 2049, 2), (16, 4, True, 37, 6), (40, 5, True, 1, 0), (8, 15, False, 2049, 12)])
+    (16, 4, True, 2049, 2), (16, 4, True, 37, 6), (40, 5, True, 1, 0), (8, 15, False, 2049, 12),
+    # the remaining tile counts NT = ceil(H / 16): 2, 4, 5, 6, 7 (5 and 7: the odd split of the output tiles), one channel,
+    # K = 1, and dilation 32768
+    (24, 7, False, 65, 1), (32, 6, True, 2049, 2), (64, 15, False, 257, 3), (72, 15, False, 2049, 2), (80, 4, True, 37, 1),
+    (96, 9, False, 129, 0), (100, 15, False, 2049, 4), (112, 1, False, 65, 0), (1, 3, False, 37, 0), (16, 15, False, 37, 15)])
 def test_conv_gradient_kernels_alone(H, K, causal, T, block):
-    """Input and weight gradient of one convolution on a seeded du: linear, so no masks.  Blocks 6 (at T = 37) and 12 have
-    dilation >= T."""
+    """Input and weight gradient of one convolution on a seeded du: linear, so no masks.  Blocks 6 (at T = 37), 12 and 15
+    have dilation >= T.  With all rows: NT = 1 .. 8 of the RAW convolution and of the NT x NT grid of tcn_wgrad_kernel."""
     B, nb = 2, block + 1
     c = dict(H=H, nb=nb, K=K, causal=causal, film=False, B=B, T=T)
     m = build(c)
