@@ -21,8 +21,10 @@ AdamW, and the reference's two clip_grad_norm_ calls.
 
 through a FROZEN MixingStyleEncoder in eval mode (`--encoder-checkpoint`, else randomly initialised).  The gradient reaches
 the TCN through the encoder's input waveform: stage A (STFT -> mel -> log) forward and backward in HIP, the conv trunk on
-PyTorch-ROCm autograd (`encoder_backend="torch"`; the hand-written eval trunk has no input gradient yet).  The mixing
-features of `out` condition the encoder as constants, as in the reference ("no grad for feature extractor").
+PyTorch-ROCm autograd (`--style-encoder torch`, the default: `encoder_backend="torch"`) or in HIP as well
+(`--style-encoder hip`: `encoder_backend="hip"` with `input_grad_backend="hip"`, the frozen encoder's input gradient on
+hand-written kernels).  The mixing features of `out` condition the encoder as constants, as in the reference ("no grad
+for feature extractor").
 With W = 0 the same seed prints the same losses: every kernel of the step has a fixed summation order."""
 import argparse
 import os
@@ -63,6 +65,8 @@ def main(argv=None):
                     help="weight of the style term 1 - cos(encoder(out), encoder(target)) through the frozen encoder (0 = off)")
     ap.add_argument("--encoder-checkpoint", default=None,
                     help="MixingStyleEncoder checkpoint (a state_dict, or a dict holding 'model_state_dict'); default: random weights")
+    ap.add_argument("--style-encoder", choices=("torch", "hip"), default="torch",
+                    help="conv trunk of the style term's encoder: PyTorch-ROCm autograd, or the hand-written HIP input gradient")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("train_tcn_mixer.py needs a GPU (backend='hip-train' has no CPU fallback)")
@@ -84,7 +88,9 @@ def main(argv=None):
     if a.style_weight > 0:   # (after everything above: the W = 0 loop draws the same random numbers as before)
         as_stems = lambda t: {s: t[:, 2 * i:2 * i + 2] for i, s in enumerate(STEMS)}
         feats = deferred_features(64).expand(a.batch_size, 64).to(dev)   # filled on the device from the encoder's own stage-A launch
-        encoder = MixingStyleEncoder(embed_dim=a.embed_dim, feature_dim=64, encoder_backend="torch")
+        encoder = MixingStyleEncoder(embed_dim=a.embed_dim, feature_dim=64, encoder_backend=a.style_encoder)
+        if a.style_encoder == "hip":
+            encoder.input_grad_backend = "hip"
         if a.encoder_checkpoint:
             sd = torch.load(a.encoder_checkpoint, map_location="cpu")
             encoder.load_state_dict(sd.get("model_state_dict", sd))

@@ -344,6 +344,38 @@ int mst_encoder_train_conv2_dgrad(const mst_encoder* enc, const float* dy2, int 
                                   const unsigned char* drop1_mask, float drop1_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Frozen encoder: the gradient of the embedding to the LOG-MEL through an encoder whose parameters are constants
+ * (eval-mode BatchNorm with the running statistics, no Dropout, FiLM from constant mixing features) -- the style term of
+ * the style-transfer trainer.  fp32 only; first-pool heights 1 and 2 (split_size < 30) and frames >= 20, as the training
+ * kernels; anything else returns an error naming the reason.  Nothing is allocated after handle creation; everything
+ * runs on the caller's stream without host synchronisation.  The handle's tables follow mst_encoder_create /
+ * mst_encoder_update_params (the eval handle's refresh).
+ *
+ * mst_encoder_forward_frozen: the eval-mode forward (same embedding as mst_encoder_forward within the forward tolerance;
+ *   other kernels) that KEEPS the raw convolution outputs and the eval affines in `workspace` for the calls below.  One
+ *   workspace per forward pass that is still to be differentiated; the backward calls read it and leave it intact, so a
+ *   pass may be differentiated any number of times.  logmel: dev [B][8][n_mels][frames] (MST_LOGMEL_REF).  emb may be NULL
+ *   (the caller runs its own head on taps->pool_in).  taps (optional): film, pool1, pool_in; events are ignored.
+ * mst_encoder_frozen_backward_apply: backward of max-pool -> ReLU -> affine of conv layer 1 or 2:
+ *   dy[band][B][C][rows][cols] = A(clip, band, ch) * dpool at the first arg-max (row-major) of every pooling window whose
+ *   maximum is positive, 0 elsewhere.  dpool: layer 1 [B][n_sub][32][H1][W1], layer 2 [B][64*n_sub*freq_dim][W2], given by
+ *   its clip / band / channel strides in floats (rows are the pooled width apart).  No FiLM gradient: the mixing
+ *   features are constants on this path.
+ * conv2 input gradient: mst_encoder_train_conv2_dgrad with drop1_mask = NULL.
+ * mst_encoder_conv1_dgrad: dy1 dev [n_sub][B][32][split_size][frames] -> dlogmel dev [B][8][n_mels][frames]: per band
+ *   the 7x7 convolution with the transposed, flipped conv1 weights on the band's own rows (exact-fp32 MFMA), then the
+ *   bands that hold a mel row added in ascending band order by one thread per element (no atomics: bit-reproducible, a
+ *   clip's result does not depend on its batch neighbours); mel rows no band covers get exact zeros.                    */
+size_t mst_encoder_frozen_workspace_bytes(const mst_encoder* enc, int B, int frames);
+int mst_encoder_forward_frozen(const mst_encoder* enc, const float* logmel, int frames, const float* feats, int B, float* emb,
+                               const mst_encoder_taps* taps, void* workspace, size_t workspace_bytes, void* stream);
+int mst_encoder_frozen_backward_apply(const mst_encoder* enc, int layer, int B, int frames, const float* dpool,
+                                      long long dp_clip, long long dp_band, long long dp_ch, float* dy, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+int mst_encoder_conv1_dgrad(const mst_encoder* enc, const float* dy1, int B, int frames, float* dlogmel, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Augmentation chain.  Replaces AudioAugmenter.augment_stems src/mixing_utils.py:376-419 and
  * apply_spectral_tilt :421-433, apply_compression :435-447, apply_bandwidth_limit :449-456,
  * apply_reverb :458-479.  Every random decision is drawn by the HOST in the reference's order

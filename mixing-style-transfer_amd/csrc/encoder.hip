@@ -211,6 +211,17 @@ struct CC<4, SUB> {  // conv2 (32 -> 64) on conv1's 2 x 40 tile geometry: the tr
   static constexpr int RL = 64;
 };
 
+template <int SUB>
+struct CC<5, SUB> {  // conv1 INPUT gradient: Conv2d(32 -> 8, 7x7, pad 3) of d(conv1 output) with the transposed, flipped weights
+                     // on the band's own split_size x frames plane; 2 x 40 tiles, raw output.  The 8 real output channels
+                     // are zero-padded to the one 16-column N-tile
+  static constexpr int CIN = 32, COUT = 16, NCH = 8, MT = 5, NT = 1;
+  static constexpr int WIN = 10, WPG = 2;
+  static constexpr int TROWS = 2, TCOLS = 40;
+  static constexpr int PR = TROWS + 6, PC = TCOLS + 6;
+  static constexpr int RL = 64;
+};
+
 struct ConvParams {
   const float* in;
   const float* wfrag;  // [nsub][NCH][WBP]   B fragments: [tap][nt][lane], zero padded to the chunk pitch
@@ -340,8 +351,8 @@ template <int LAYER, int SUB, int MODE = 0>
 __global__ __launch_bounds__(kConvThreads) void conv_kernel(const ConvParams p) {
   using C = CC<LAYER, SUB>;
   using GEO = ConvGeom<LAYER, SUB>;
-  static_assert(MODE == 0 || (MODE == 1 && LAYER <= 2) || (MODE == 2 && LAYER == 3) || (MODE == 3 && LAYER == 4),
-                "raw modes: forward layers, conv2 dgrad, conv2 strip");
+  static_assert(MODE == 0 || (MODE == 1 && LAYER <= 2) || (MODE == 2 && (LAYER == 3 || LAYER == 5)) || (MODE == 3 && LAYER == 4),
+                "raw modes: forward layers, conv2 / conv1 dgrad, conv2 strip");
   constexpr bool GEO1 = LAYER == 1 || LAYER >= 3;   // 2 x 40 tiles, pooling-window accumulator order
   constexpr int MT = C::MT, NT = C::NT, NCH = C::NCH, PR = C::PR, PC = C::PC, RL = C::RL;
   constexpr int WBP = GEO::WBP, PATCH = GEO::PATCH, NWF = GEO::NWF, NPF = GEO::NPF, NCV = GEO::NCV;
@@ -354,6 +365,9 @@ __global__ __launch_bounds__(kConvThreads) void conv_kernel(const ConvParams p) 
   constexpr bool BL = LAYER == 2;
   constexpr int NPFK = BL ? 16 : NPF;
   constexpr int NPIECE = NPFK + NWF, PPT = (NPIECE + 48) / 49;  // prefetch pieces, pieces issued per tap
+  // issue slots per tap: one per MFMA, and at least one per fragment read and prefetch piece (a single N-tile -- the conv1 input
+  // gradient -- has fewer MFMAs than reads: its last slots carry no MFMA)
+  constexpr int NSLOT = MT * NT > MT + NT + PPT ? MT * NT : MT + NT + PPT;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: tile bookkeeping stays on the SALU
@@ -567,11 +581,11 @@ __global__ __launch_bounds__(kConvThreads) void conv_kernel(const ConvParams p) 
           // hand-interleaved issue order, pinned by sched_barrier: after every MFMA one LDS read of the next tap's
           // fragments (or a global prefetch load of the next chunk) is issued into the shadow of that MFMA
 #pragma unroll
-          for (int i = 0; i < MT * NT; ++i) {
+          for (int i = 0; i < NSLOT; ++i) {
             const int t = i / NT, n = i % NT;
             // (no per-MFMA skipping of M-tiles past the plane: a wave-uniform branch here cost the training forward half its
             // speed; the last rows of a 10-row plane go through the strip kernel, MODE 3, and otherwise padding rows are computed)
-            if (!(SKIP0 && t == 0)) acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[cu][t], b[cu][n], acc[t][n], 0, 0, 0);
+            if (i < MT * NT && !(SKIP0 && t == 0)) acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[cu][t], b[cu][n], acc[t][n], 0, 0, 0);
             if (tap + 1 < 49) {
               if (i < NT) b[nx][i] = wb[((tap + 1) * NT + i) * 64 + lane];   // B first: needed by the next tap's MFMA 0
               else if (i < MT + NT) a[nx][i - NT] = pbuf[abase[i - NT] + off];
@@ -655,12 +669,15 @@ __global__ __launch_bounds__(kConvThreads) void conv_kernel(const ConvParams p) 
     }
     if (MODE == 2 && chunk == NCH - 1 && cur.valid) {
       // conv2 input gradient: raw values to the pool1-shaped tensor, Dropout mask applied on the way out
+      // (conv1 input gradient: the 8 real channels of the N-tile to [clip][band][8][rows][cols])
+      constexpr int CO = LAYER == 5 ? 8 : C::COUT;
       const int j = lane & 15, g = lane >> 4;
 #pragma unroll
       for (int n = 0; n < NT; ++n) {
         const int ch = n * 16 + j;
-        float* ob = p.out + (((size_t)cur.clip * p.nsub + cur.band) * C::COUT + ch) * (size_t)p.raw_rows * p.raw_cols;
-        const unsigned char* mb = p.mask ? p.mask + (((size_t)cur.clip * p.nsub + cur.band) * C::COUT + ch) * (size_t)p.raw_rows * p.raw_cols
+        if (ch >= CO) continue;
+        float* ob = p.out + (((size_t)cur.clip * p.nsub + cur.band) * CO + ch) * (size_t)p.raw_rows * p.raw_cols;
+        const unsigned char* mb = p.mask ? p.mask + (((size_t)cur.clip * p.nsub + cur.band) * CO + ch) * (size_t)p.raw_rows * p.raw_cols
                                          : nullptr;
 #pragma unroll
         for (int e = 0; e < 4 * MT; ++e) {
@@ -2791,6 +2808,8 @@ struct mst_encoder {
   // un-folded parameters for the training forward (batch-statistics BatchNorm)
   float *c1b = nullptr, *bn1w = nullptr, *bn1b = nullptr, *c2b = nullptr, *bn2w = nullptr, *bn2b = nullptr;
   float* w2dfrag = nullptr;   // conv2 input-gradient weight fragments [nsub][16][WBP] (refreshed by update_trunk_params)
+  float* w1dfrag = nullptr;   // conv1 input-gradient weight fragments [nsub][8][WBP] (likewise)
+  float* zero_bias = nullptr; // [nsub][64] zeros: the frozen forward's raw kernels add no bias (the eval affines carry it)
   // f16-operand training (mst_encoder_set_train_precision): fragments and pre-scales rebuilt on the device every step
   int train_f16 = 0;
   void* w2dfrag16 = nullptr;  // conv2 input-gradient fragments, hi only: [nsub][8 chunks][13 steps][2 nt][lane][8]
@@ -3759,21 +3778,84 @@ __global__ void conv_fragments_kernel(const float* w, float* f, int nsub, int co
   f[((size_t)b * nch + ch) * wchp + ((size_t)tap * nt + n) * 64 + lane] = w[(((size_t)b * cout + co) * cin + ci) * 49 + tap];
 }
 
-// conv2 weights [nsub][64 co][32 ci][49] -> B fragments of the input-gradient convolution (64 -> 32, flipped taps):
-// f[band][chunk c][tap][nt][lane] = W2[co = 4 c + (lane >> 4)][ci = 16 nt + (lane & 15)][48 - tap]
-__global__ void dgrad_fragments_kernel(const float* w, float* f, int nsub, int wchp) {
-  const long long total = (long long)nsub * 16 * 49 * 2 * 64;
+// conv weights [nsub][cout co][cin ci][49] -> B fragments of the input-gradient convolution (cout -> cin, flipped taps):
+// f[band][chunk c][tap][nt][lane] = W[co = 4 c + (lane >> 4)][ci = 16 nt + (lane & 15)][48 - tap], zero for ci >= cin
+// (conv2: 64 -> 32, two N-tiles; conv1: 32 -> 8, one N-tile whose upper half is padding)
+__global__ void dgrad_fragments_kernel(const float* w, float* f, int nsub, int cout, int cin, int wchp) {
+  const int nch = cout / 4, nt = (cin + 15) / 16;
+  const long long total = (long long)nsub * nch * 49 * nt * 64;
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   const int lane = (int)(i & 63);
   long long r = i >> 6;
-  const int n = (int)(r % 2);
-  r /= 2;
+  const int n = (int)(r % nt);
+  r /= nt;
   const int tap = (int)(r % 49);
   r /= 49;
-  const int ch = (int)(r % 16), b = (int)(r / 16);
+  const int ch = (int)(r % nch), b = (int)(r / nch);
   const int co = 4 * ch + (lane >> 4), ci = n * 16 + (lane & 15);
-  f[((size_t)b * 16 + ch) * wchp + ((size_t)tap * 2 + n) * 64 + lane] = w[(((size_t)b * 64 + co) * 32 + ci) * 49 + (48 - tap)];
+  f[((size_t)b * nch + ch) * wchp + ((size_t)tap * nt + n) * 64 + lane] =
+      ci < cin ? w[(((size_t)b * cout + co) * cin + ci) * 49 + (48 - tap)] : 0.f;
+}
+hipError_t launch_dgrad_fragments(const mst_encoder* e, const float* conv1_w, const float* conv2_w, hipStream_t st) {
+  const int ns = e->cfg.n_subbands;
+  const long long t2 = (long long)ns * 16 * 49 * 2 * 64, t1 = (long long)ns * 8 * 49 * 1 * 64;
+  hipLaunchKernelGGL(dgrad_fragments_kernel, dim3((unsigned)((t2 + 255) / 256)), dim3(256), 0, st, conv2_w, e->w2dfrag, ns, 64, 32,
+                     ConvGeom<3, 2>::WBP);
+  hipLaunchKernelGGL(dgrad_fragments_kernel, dim3((unsigned)((t1 + 255) / 256)), dim3(256), 0, st, conv1_w, e->w1dfrag, ns, 32, 8,
+                     ConvGeom<5, 2>::WBP);
+  return hipGetLastError();
+}
+
+// ---- frozen encoder (eval-mode BatchNorm, constant FiLM): backward of max-pool -> ReLU -> affine.  With frozen statistics the
+// BatchNorm backward has no batch terms:  dy = A * df  (A = the eval affine's slope, df from unit_df: dpool at the first
+// arg-max of every window with a positive maximum).  One pass, no sums; the raw outputs are read only.
+template <int LAYER, int SUB>
+__global__ __launch_bounds__(256) void frozen_bwd_kernel(const ApplyBwdParams p, long long units) {
+  using C = CC<LAYER, SUB>;
+  constexpr int NT = C::NT, NV = 4 * C::MT;
+  const long long u = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (u >= units) return;
+  const int lane = (int)(u & 63), n = (int)((u >> 6) % NT);
+  long long tile = (u >> 6) / NT;
+  const int tc = (int)(tile % p.tiles_c);
+  tile /= p.tiles_c;
+  const int tr = (int)(tile % p.tiles_r);
+  tile /= p.tiles_r;
+  const int band = (int)(tile % p.nsub), clip = (int)(tile / p.nsub);
+  const int j = lane & 15, g = lane >> 4, ch = n * 16 + j;
+  const float2 ac = p.aff[((size_t)clip * p.nsub + band) * C::COUT + ch];
+  float v[NV], df[NV];
+  load_unit<NV>(p.yraw, nullptr, band, (size_t)u, v);
+  unit_df<LAYER, SUB>(p, v, ac, clip, band, ch, tr, tc, g, df);
+  float* dyb = p.dy + (((size_t)band * p.B + clip) * C::COUT + ch) * (size_t)p.rows * p.cols;
+#pragma unroll
+  for (int e = 0; e < NV; ++e) {
+    int row, col;
+    unit_geometry<LAYER, SUB>(tr, tc, g, e, row, col);
+    if (row < p.rows && col < p.cols) dyb[(size_t)row * p.cols + col] = ac.x * df[e];
+  }
+}
+
+// d logmel[clip][ci][mel][frame] = the bands' input gradients dxb[clip][band][ci][mel - band * overlap][frame] added in
+// ASCENDING band order (one thread per element: no atomics, the same bits every time); a mel row no band covers gets 0
+__global__ __launch_bounds__(256) void band_fold_kernel(const float* __restrict__ dxb, float* __restrict__ dlm, long long total,
+                                                        int nsub, int R, int overlap, int n_mels, int frames) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int col = (int)(i % frames);
+  long long r = i / frames;
+  const int mel = (int)(r % n_mels);
+  r /= n_mels;
+  const int ci = (int)(r % 8);
+  const long long clip = r / 8;
+  const int k1 = min(nsub - 1, mel / overlap);
+  float s = 0.f;
+  for (int k = max(0, (mel - R + overlap) / overlap); k <= k1; ++k) {
+    const int br = mel - k * overlap;
+    if (br >= 0 && br < R) s += dxb[((((size_t)clip * nsub + k) * 8 + ci) * R + br) * (size_t)frames + col];
+  }
+  dlm[i] = s;
 }
 
 template <int LAYER, int SUB, int MODE = 0>
@@ -4017,17 +4099,22 @@ int mst_encoder_create(mst_encoder** out, const mst_encoder_config* cfg, const m
   UPP(att0_b, w->att0_b, A); UPP(att2_w, w->att2_w, A); UPP(proj_b, w->proj_b, E); UPP(att2_b, w->att2_b, 1);
   UPP(c1b, w->conv1_b, ns * 32); UPP(bn1w, w->bn1_w, ns * 32); UPP(bn1b, w->bn1_b, ns * 32);
   UPP(c2b, w->conv2_b, ns * 64); UPP(bn2w, w->bn2_w, ns * 64); UPP(bn2b, w->bn2_b, ns * 64);
-  if (!rc) {   // input-gradient fragments of conv2, built on the device from a temporary copy of the weights
-    float* tmp = nullptr;
-    rc = mst::upload(&tmp, w->conv2_w, (size_t)ns * 64 * 32 * 49);
-    if (!rc && hipMalloc(&e->w2dfrag, (size_t)ns * 16 * ConvGeom<3, 2>::WBP * sizeof(float)) != hipSuccess) rc = MST_ENOMEM;
+  if (!rc) {   // input-gradient fragments of conv2 and conv1, built on the device from temporary copies of the weights
+    float *tmp2 = nullptr, *tmp1 = nullptr;
+    const size_t n2 = (size_t)ns * 16 * ConvGeom<3, 2>::WBP, n1 = (size_t)ns * 8 * ConvGeom<5, 2>::WBP;
+    rc = mst::upload(&tmp2, w->conv2_w, (size_t)ns * 64 * 32 * 49);
+    if (!rc) rc = mst::upload(&tmp1, w->conv1_w, (size_t)ns * 32 * 8 * 49);
+    if (!rc && (hipMalloc(&e->w2dfrag, n2 * sizeof(float)) != hipSuccess || hipMalloc(&e->w1dfrag, n1 * sizeof(float)) != hipSuccess ||
+                hipMalloc(&e->zero_bias, (size_t)ns * 64 * sizeof(float)) != hipSuccess))
+      rc = MST_ENOMEM;
     if (!rc) {
-      (void)hipMemset(e->w2dfrag, 0, (size_t)ns * 16 * ConvGeom<3, 2>::WBP * sizeof(float));
-      const long long t3 = (long long)ns * 16 * 49 * 2 * 64;
-      hipLaunchKernelGGL(dgrad_fragments_kernel, dim3((unsigned)((t3 + 255) / 256)), dim3(256), 0, 0, tmp, e->w2dfrag, ns, ConvGeom<3, 2>::WBP);
+      (void)hipMemset(e->w2dfrag, 0, n2 * sizeof(float));
+      (void)hipMemset(e->w1dfrag, 0, n1 * sizeof(float));
+      (void)hipMemset(e->zero_bias, 0, (size_t)ns * 64 * sizeof(float));
+      if (launch_dgrad_fragments(e, tmp1, tmp2, 0) != hipSuccess) rc = MST_EHIP;
       (void)hipDeviceSynchronize();
     }
-    (void)hipFree(tmp);
+    (void)hipFree(tmp2), (void)hipFree(tmp1);
   }
 #undef UP
 #undef UPP
@@ -4043,7 +4130,7 @@ void mst_encoder_destroy(mst_encoder* e) {
   if (!e) return;
   float* ptrs[] = {e->w1frag, e->w2frag, e->s1, e->t1, e->s2, e->t2, e->w0t, e->b0, e->w3t, e->b3, e->hwt,
                    e->hb, e->att0frag, e->att0_b, e->att2_w, e->projfrag, e->proj_b, e->c1b, e->bn1w, e->bn1b, e->c2b,
-                   e->bn2w, e->bn2b, e->w2dfrag, e->att2_b, e->f16_wsc1e, e->f16_wsc2e, e->w2norm_e};
+                   e->bn2w, e->bn2b, e->w2dfrag, e->w1dfrag, e->zero_bias, e->att2_b, e->f16_wsc1e, e->f16_wsc2e, e->w2norm_e};
   for (float* q : ptrs) (void)hipFree(q);
   (void)hipFree(e->w1frag16), (void)hipFree(e->w1frag16e);
   (void)hipFree(e->w1norm), (void)hipFree(e->f16_winv1), (void)hipFree(e->f16_winv2);
@@ -4719,10 +4806,7 @@ int mst_encoder_update_trunk_params(mst_encoder* e, const float* conv1_w, const 
                        ConvGeom<1, 2>::WBP);
     hipLaunchKernelGGL(conv_fragments_kernel, dim3((unsigned)((t2 + 255) / 256)), dim3(256), 0, st, conv2_w, e->w2frag, ns, 64, 32,
                        ConvGeom<2, 2>::WBP);
-    const long long t3 = (long long)ns * 16 * 49 * 2 * 64;
-    hipLaunchKernelGGL(dgrad_fragments_kernel, dim3((unsigned)((t3 + 255) / 256)), dim3(256), 0, st, conv2_w, e->w2dfrag, ns,
-                       ConvGeom<3, 2>::WBP);
-    MST_HIP_CHECK(hipGetLastError());
+    MST_HIP_CHECK(launch_dgrad_fragments(e, conv1_w, conv2_w, st));
   }
   if (train_fwd16(e)) {   // f16 fragments of the new weights: per-channel power-of-two pre-scale, then hi/lo (forward) / hi (dgrad)
     hipLaunchKernelGGL(f16_wstats_kernel, dim3(ns * 32), dim3(64), 0, st, conv1_w, 32, (long long)32 * 392, 392, 1, 0, 392,
@@ -4965,6 +5049,185 @@ int mst_encoder_train_conv2_dgrad(const mst_encoder* e, const float* dy2, int B,
     return MST_OK;
   }
   MST_HIP_CHECK(launch_conv<3, 2, 2>(cp, g, st));
+  return MST_OK;
+}
+
+// ---- frozen encoder: the eval-mode forward with the raw convolution outputs kept, and the gradient to the log-mel ------------
+// (DESIGN 3.10).  The parameters are constants (eval BatchNorm, no Dropout, FiLM from constant mixing features), so the affines
+// are the eval forward's (launch_film) and the backward of a layer is one element-wise pass (frozen_bwd_kernel) followed by
+// the input-gradient convolution.  The raw kernels get a ZERO bias: the eval affine's C already holds the convolution bias.
+namespace {
+struct FrozenLayout {
+  WsLayout base;
+  size_t y1, y2, stats, dxb, total;
+  int tr1, tc1, tr2, tc2;
+};
+FrozenLayout frozen_layout(const mst_encoder* e, int B, int frames) {
+  FrozenLayout F{};
+  F.base = ws_layout(e, B, frames);
+  const int ns = e->cfg.n_subbands;
+  const int tcols1 = e->sub == 2 ? 40 : 80;                    // conv1 tiles as in the fp32 training forward: 2 x 40 or 1 x 80
+  F.tr1 = e->sub == 2 ? e->cfg.split_size / 2 : e->H1, F.tc1 = (frames + tcols1 - 1) / tcols1;
+  F.tr2 = (e->H1 + 7) / 8, F.tc2 = (F.base.W1 + 7) / 8;
+  size_t o = F.base.total;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o += mst::align_up(bytes, 256);
+    return at;
+  };
+  F.y1 = take((size_t)B * ns * F.tr1 * F.tc1 * 2 * 64 * 20 * 4);
+  F.y2 = take((size_t)B * ns * F.tr2 * F.tc2 * 4 * 64 * 16 * 4);
+  F.stats = take((size_t)ns * 64 * 2 * sizeof(mst::DetAcc));   // the raw kernels' batch sums: written, never read
+  F.dxb = take((size_t)B * ns * 8 * e->cfg.split_size * frames * 4);   // conv1 input gradient per band, before the band fold
+  F.total = o;
+  return F;
+}
+// what every frozen entry point checks; fills the layout
+int frozen_check(const char* who, const mst_encoder* e, int B, int frames, const void* workspace, size_t workspace_bytes, FrozenLayout* F) {
+  MST_REQUIRE(e, "%s: NULL encoder", who);
+  MST_REQUIRE(e->sub <= 2, "%s: the frozen-encoder kernels cover first-pool heights 1 and 2 (split_size=%d)", who, e->cfg.split_size);
+  MST_REQUIRE(e->conv1_f16x3 == 0 && e->train_f16 == 0, "%s: the frozen-encoder path is fp32 only (conv precision mode %d, training mode %d)",
+              who, e->conv1_f16x3, e->train_f16);
+  MST_REQUIRE(B > 0 && frames >= 20, "%s: need B>0 and frames>=20 (B=%d frames=%d)", who, B, frames);
+  *F = frozen_layout(e, B, frames);
+  if (!workspace || workspace_bytes < F->total)
+    return mst::fail(MST_ENOMEM, "%s: workspace %zu B < required %zu B", who, workspace_bytes, F->total);
+  return MST_OK;
+}
+}  // namespace
+
+size_t mst_encoder_frozen_workspace_bytes(const mst_encoder* e, int B, int frames) {
+  if (!e || B <= 0 || frames < 20 || e->sub > 2 || e->conv1_f16x3 || e->train_f16) return 0;
+  return frozen_layout(e, B, frames).total;
+}
+
+int mst_encoder_forward_frozen(const mst_encoder* e, const float* logmel, int frames, const float* feats, int B, float* emb,
+                               const mst_encoder_taps* taps, void* workspace, size_t workspace_bytes, void* stream) {
+  MST_REQUIRE(e && logmel && feats, "mst_encoder_forward_frozen: NULL argument");
+  FrozenLayout F;
+  if (const int rc = frozen_check("mst_encoder_forward_frozen", e, B, frames, workspace, workspace_bytes, &F)) return rc;
+  const WsLayout& L = F.base;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  char* ws = reinterpret_cast<char*>(workspace);
+  const int ns = e->cfg.n_subbands;
+  float* film = reinterpret_cast<float*>(ws + L.film);
+  float* pool1 = (taps && taps->pool1) ? taps->pool1 : reinterpret_cast<float*>(ws + L.pool1);
+  float* pool_in = (taps && taps->pool_in) ? taps->pool_in : reinterpret_cast<float*>(ws + L.pool_in);
+  float2* aff1 = reinterpret_cast<float2*>(ws + L.aff1);   // the EVAL affines (running statistics, bias and FiLM folded): kept for the backward
+  float2* aff2 = reinterpret_cast<float2*>(ws + L.aff2);
+  float* y1 = reinterpret_cast<float*>(ws + F.y1);
+  float* y2 = reinterpret_cast<float*>(ws + F.y2);
+  mst::DetAcc* stats = reinterpret_cast<mst::DetAcc*>(ws + F.stats);
+  MST_HIP_CHECK(hipMemsetAsync(stats, 0, (size_t)ns * 64 * 2 * sizeof(mst::DetAcc), st));
+  MST_HIP_CHECK(launch_film(film_params(e, feats, film, aff1, aff2, reinterpret_cast<float*>(ws + L.film_h2), B), st));
+  const int grid = e->num_cus;
+  const dim3 blk(kConvThreads);
+  {   // conv1 raw (no bias), then eval affine + ReLU + max-pool
+    ConvParams cp{};
+    cp.in = logmel, cp.wfrag = e->w1frag, cp.B = B, cp.nsub = ns;
+    conv1_input_geometry(cp, e, frames);
+    cp.out_rows = e->H1, cp.out_cols = L.W1;
+    cp.tiles_r = F.tr1, cp.tiles_c = F.tc1;
+    cp.sets_per_band = sets_per_band(B, cp.tiles_r, cp.tiles_c);
+    cp.yraw = y1, cp.stats = stats, cp.bias = e->zero_bias, cp.raw_rows = e->cfg.split_size, cp.raw_cols = frames;
+    cp.acc_tr = F.tr1, cp.acc_tc = F.tc1;
+    const int g = std::min(grid, ns * cp.sets_per_band);
+    if (e->sub == 2) MST_HIP_CHECK(mst::launch_lds<conv1_resident_kernel<2, 1>>(dim3(g), blk, kConv1ResidentLds<2>, st, cp));
+    else MST_HIP_CHECK(launch_conv<1, 1, 1>(cp, g, st));
+    ApplyParams ap{y1, e->cfg.split_size, aff1, pool1, nullptr, 1.f, B, ns, F.tr1, F.tc1, e->H1, L.W1,
+                   (long long)B * ns * F.tr1 * F.tc1 * 2 * 64, nullptr, nullptr, frames};
+    ap.pool_h = e->sub;
+    if (e->sub == 2) hipLaunchKernelGGL((apply_kernel<1, 2>), dim3((unsigned)((ap.units + 255) / 256)), dim3(256), 0, st, ap);
+    else hipLaunchKernelGGL((apply_kernel<1, 1>), dim3((unsigned)((ap.units + 255) / 256)), dim3(256), 0, st, ap);
+    MST_HIP_CHECK(hipGetLastError());
+  }
+  {   // conv2 raw (8 x 8 tiles, the last one or two rows through the strip kernel), then eval affine + ReLU + max-pool
+    ConvParams cp{};
+    cp.in = pool1, cp.wfrag = e->w2frag, cp.B = B, cp.nsub = ns;
+    conv2_input_geometry(cp, e, L.W1);
+    cp.out_rows = e->FD, cp.out_cols = L.W2;
+    const int rows_last = e->H1 - 8 * (F.tr2 - 1);
+    const bool strip = F.tr2 >= 2 && rows_last <= 2;
+    cp.tiles_r = strip ? F.tr2 - 1 : F.tr2, cp.tiles_c = F.tc2;
+    cp.sets_per_band = sets_per_band(B, cp.tiles_r, cp.tiles_c);
+    cp.yraw = y2, cp.stats = stats, cp.bias = e->zero_bias, cp.raw_rows = e->H1, cp.raw_cols = L.W1;
+    cp.acc_tr = F.tr2, cp.acc_tc = F.tc2;
+    MST_HIP_CHECK(launch_conv<2, 2, 1>(cp, std::min(grid, ns * cp.sets_per_band), st));
+    if (strip) {
+      ConvParams sp = cp;
+      sp.row_off = 8 * (F.tr2 - 1);
+      sp.tiles_r = (rows_last + 1) / 2, sp.tiles_c = (L.W1 + 39) / 40;
+      sp.sets_per_band = sets_per_band(B, sp.tiles_r, sp.tiles_c);
+      MST_HIP_CHECK(launch_conv<4, 2, 3>(sp, std::min(grid, ns * sp.sets_per_band), st));
+    }
+    ApplyParams ap{y2, e->H1, aff2, pool_in, nullptr, 1.f, B, ns, F.tr2, F.tc2, e->FD, L.W2, (long long)B * ns * F.tr2 * F.tc2 * 4 * 64,
+                   nullptr, nullptr, L.W1};
+    hipLaunchKernelGGL((apply_kernel<2, 2>), dim3((unsigned)((ap.units + 255) / 256)), dim3(256), 0, st, ap);
+    MST_HIP_CHECK(hipGetLastError());
+  }
+  if (emb) {
+    if (const int rc = launch_head(e, L, ws, pool_in, emb, B, st)) return rc;
+  }
+  if (taps && taps->film) MST_HIP_CHECK(hipMemcpyAsync(taps->film, film, (size_t)B * ns * 192 * 4, hipMemcpyDeviceToDevice, st));
+  return MST_OK;
+}
+
+int mst_encoder_frozen_backward_apply(const mst_encoder* e, int layer, int B, int frames, const float* dpool, long long dp_clip,
+                                      long long dp_band, long long dp_ch, float* dy, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  MST_REQUIRE(e && dpool && dy && (layer == 1 || layer == 2), "mst_encoder_frozen_backward_apply: bad arguments");
+  FrozenLayout F;
+  if (const int rc = frozen_check("mst_encoder_frozen_backward_apply", e, B, frames, workspace, workspace_bytes, &F)) return rc;
+  const WsLayout& L = F.base;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const char* ws = reinterpret_cast<const char*>(workspace);
+  const int ns = e->cfg.n_subbands;
+  ApplyBwdParams p{};
+  p.dpool = dpool, p.dp_clip = dp_clip, p.dp_band = dp_band, p.dp_ch = dp_ch;
+  p.dy = dy, p.B = B, p.nsub = ns, p.pool_h = e->sub;
+  if (layer == 1) {
+    p.yraw = reinterpret_cast<const float*>(ws + F.y1), p.aff = reinterpret_cast<const float2*>(ws + L.aff1);
+    p.dp_rows = e->H1, p.dp_cols = L.W1, p.tiles_r = F.tr1, p.tiles_c = F.tc1;
+    p.rows = e->cfg.split_size, p.cols = frames;
+  } else {
+    p.yraw = reinterpret_cast<const float*>(ws + F.y2), p.aff = reinterpret_cast<const float2*>(ws + L.aff2);
+    p.dp_rows = e->FD, p.dp_cols = L.W2, p.tiles_r = F.tr2, p.tiles_c = F.tc2;
+    p.rows = e->H1, p.cols = L.W1;
+  }
+  const long long units = (long long)B * ns * p.tiles_r * p.tiles_c * (layer == 1 ? 2 : 4) * 64;
+  const dim3 gd((unsigned)((units + 255) / 256));
+  if (layer == 1 && e->sub == 2) hipLaunchKernelGGL((frozen_bwd_kernel<1, 2>), gd, dim3(256), 0, st, p, units);
+  else if (layer == 1) hipLaunchKernelGGL((frozen_bwd_kernel<1, 1>), gd, dim3(256), 0, st, p, units);
+  else hipLaunchKernelGGL((frozen_bwd_kernel<2, 2>), gd, dim3(256), 0, st, p, units);
+  MST_HIP_CHECK(hipGetLastError());
+  return MST_OK;
+}
+
+int mst_encoder_conv1_dgrad(const mst_encoder* e, const float* dy1, int B, int frames, float* dlogmel, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  MST_REQUIRE(e && dy1 && dlogmel, "mst_encoder_conv1_dgrad: NULL argument");
+  FrozenLayout F;
+  if (const int rc = frozen_check("mst_encoder_conv1_dgrad", e, B, frames, workspace, workspace_bytes, &F)) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int ns = e->cfg.n_subbands, R = e->cfg.split_size;
+  float* dxb = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + F.dxb);
+  const long long bandoff = (long long)B * 32 * R * frames;   // dy1 is [band][B][32][R][frames]
+  MST_REQUIRE(bandoff * ns < (1LL << 31), "mst_encoder_conv1_dgrad: batch too large for 32-bit band offsets");
+  ConvParams cp{};
+  cp.in = dy1, cp.wfrag = e->w1dfrag, cp.out = dxb, cp.B = B, cp.nsub = ns;
+  cp.in_rows = R, cp.in_cols = frames;
+  cp.in_cstride = R * frames;
+  cp.in_bandoff = (int)bandoff;
+  cp.in_clipstride = (long long)32 * R * frames;
+  cp.out_rows = R, cp.out_cols = frames;
+  cp.tiles_r = (R + 1) / 2, cp.tiles_c = (frames + 39) / 40;
+  cp.sets_per_band = sets_per_band(B, cp.tiles_r, cp.tiles_c);
+  cp.raw_rows = R, cp.raw_cols = frames, cp.mask = nullptr, cp.mask_scale = 1.f;
+  MST_HIP_CHECK(launch_conv<5, 2, 2>(cp, std::min(e->num_cus, ns * cp.sets_per_band), st));
+  const long long total = (long long)B * 8 * e->cfg.n_mels * frames;
+  hipLaunchKernelGGL(band_fold_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, dxb, dlogmel, total, ns, R,
+                     e->cfg.overlap, e->cfg.n_mels, frames);
+  MST_HIP_CHECK(hipGetLastError());
   return MST_OK;
 }
 

@@ -14,8 +14,11 @@ Forward paths
     PyTorch-ROCm autograd (the path the gradients are tested against), `"hip-or-torch"` warns once per reason and falls back.
   * gradient to the WAVEFORM (a stem requires grad and grad is enabled -- the style term of the style-transfer trainer through
     a frozen encoder): stage A forward and backward in HIP (`_LogMelHip`, `mst_logmel_backward`), the conv trunk on
-    PyTorch-ROCm autograd with `encoder_backend = "torch"`; `encoder_backend = "hip"` raises (the hand-written eval trunk has
-    no input gradient yet).  The mixing features of the same launch are constants.
+    PyTorch-ROCm autograd with `encoder_backend = "torch"`, or -- `encoder_backend = "hip"` with `input_grad_backend = "hip"`,
+    eval mode, every parameter frozen -- trunk and head in libmst.so too (`_HipFrozenTrunk`: eval-mode forward that keeps the raw
+    conv outputs, backward = pool / ReLU / affine pass, conv2 and conv1 input gradients; `_HipHead`).  With the default
+    `input_grad_backend = "none"`, `encoder_backend = "hip"` raises for such a call.  The mixing features of the same launch
+    are constants.
 """
 import ctypes as C
 
@@ -530,6 +533,75 @@ class HipEncoder:
                                                        _lib.stream_ptr(dy2.device)), "mst_encoder_train_conv2_dgrad")
         return out
 
+    def frozen_workspace(self, B, frames, device):
+        """A fresh workspace for one frozen forward pass and its backward calls (`mst_encoder_frozen_workspace_bytes`)."""
+        need = _lib.lib().mst_encoder_frozen_workspace_bytes(self._h, B, frames)
+        if need == 0:
+            raise _lib.MstError(f"the frozen-encoder kernels (fp32, first-pool heights 1 and 2, frames >= 20) cannot take "
+                                f"split_size={self.split}, frames={frames}, conv precision mode {self.mode}")
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+        if _POISON_WS:
+            ws.fill_(255)
+        return ws
+
+    def forward_frozen(self, logmel, feats, head=True, ws=None):
+        """Eval-mode forward that keeps the raw convolution outputs for the gradient to the log-mel
+        (`mst_encoder_forward_frozen`).  logmel (B, 8, n_mels, frames) fp32, reference layout.  Returns (emb or None, taps with
+        film / pool1 / pool_in, workspace): the workspace belongs to this pass; `frozen_backward_apply` and `conv1_dgrad`
+        read it and leave it intact."""
+        L = _lib.lib()
+        lm = logmel.detach().contiguous().float()
+        B, _, M, Fr = lm.shape
+        dev = lm.device
+        if ws is None:
+            ws = self.frozen_workspace(B, Fr, dev)
+        H1, W1 = self.split // self.sub, Fr // 5
+        out = dict(film=torch.empty(B, self.n_sub * 192, device=dev), pool1=torch.empty(B, self.n_sub, 32, H1, W1, device=dev),
+                   pool_in=torch.empty(B, 64 * self.n_sub * self.freq_dim, W1 // 4, device=dev))
+        taps = _lib.EncoderTaps(out["film"].data_ptr(), out["pool1"].data_ptr(), out["pool_in"].data_ptr())
+        emb = torch.empty(B, self.embed_dim, device=dev) if head else None
+        with torch.cuda.device(dev):
+            _lib.check(L.mst_encoder_forward_frozen(self._h, _lib.dptr(lm), Fr, _lib.dptr(feats.detach().contiguous().float()), B,
+                                                    _lib.dptr(emb), C.byref(taps), _lib.dptr(ws), ws.numel(), _lib.stream_ptr(dev)),
+                       "mst_encoder_forward_frozen")
+        return emb, out, ws
+
+    def frozen_backward_apply(self, layer, dpool, B, frames, ws):
+        """d(conv output) (n_sub, B, C, rows, cols) of conv layer 1 / 2 from the gradient of its pooled activation: A * dpool at
+        the arg-max of every window with a positive maximum (`mst_encoder_frozen_backward_apply`).  dpool: layer 1
+        (B, n_sub, 32, H1, W1), layer 2 (B, 64 * n_sub * freq_dim, W2).  `ws`: the workspace `forward_frozen` returned."""
+        L = _lib.lib()
+        dev = dpool.device
+        dpool = dpool.contiguous().float()
+        W1 = frames // 5
+        if layer == 1:
+            st = (dpool.stride(0), dpool.stride(1), dpool.stride(2))
+            dy = torch.empty(self.n_sub, B, 32, self.split, frames, device=dev)
+        else:
+            W2 = W1 // 4
+            st = (dpool.shape[1] * W2, 64 * self.freq_dim * W2, self.freq_dim * W2)
+            dy = torch.empty(self.n_sub, B, 64, self.split // self.sub, W1, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.mst_encoder_frozen_backward_apply(self._h, layer, B, frames, _lib.dptr(dpool), st[0], st[1], st[2],
+                                                           _lib.dptr(dy), _lib.dptr(ws), ws.numel(), _lib.stream_ptr(dev)),
+                       "mst_encoder_frozen_backward_apply")
+        return dy
+
+    def conv1_dgrad(self, dy1, B, frames, ws=None):
+        """gradient of the log-mel (B, 8, n_mels, frames) from dy1 (n_sub, B, 32, split_size, frames): per band the 7x7
+        convolution with the transposed, flipped conv1 weights, then the bands added in ascending order
+        (`mst_encoder_conv1_dgrad`).  `ws`: a frozen workspace (its per-band scratch is used), or None for a fresh one."""
+        L = _lib.lib()
+        dev = dy1.device
+        dy1 = dy1.contiguous().float()
+        if ws is None:
+            ws = self.frozen_workspace(B, frames, dev)
+        out = torch.empty(B, 8, self.cfg.n_mels, frames, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.mst_encoder_conv1_dgrad(self._h, _lib.dptr(dy1), B, frames, _lib.dptr(out), _lib.dptr(ws), ws.numel(),
+                                                 _lib.stream_ptr(dev)), "mst_encoder_conv1_dgrad")
+        return out
+
     def conv2_wgrad(self, pool1, B, frames):
         """conv2 weight gradient (n_sub, 64, 32, 7, 7) from the accumulator-order d(conv2 output) in the workspace.
         pool1 None (float16 training modes): the operand is the float16 pool1 the forward pass left in the workspace."""
@@ -777,6 +849,49 @@ class _HipTrunk(torch.autograd.Function):
         return (None, None, dfilm, None, None, None, None, None) + tuple(g[i] for g in fams for i in range(ns))
 
 
+class _HipFrozenTrunk(torch.autograd.Function):
+    """The conv trunk of a FROZEN encoder (eval-mode BatchNorm, no Dropout, constant mixing features) with the gradient to the
+    log-mel: (enc, logmel, feats) -> pool_in.  Forward: `mst_encoder_forward_frozen` (raw conv outputs and the eval affines kept in
+    a workspace this pass owns).  Backward: `frozen_backward_apply(2)` -> `conv2_dgrad` -> `frozen_backward_apply(1)` ->
+    `conv1_dgrad`; it reads the workspace and leaves it intact, so a retained graph can be differentiated again.  The weight
+    fragments are the eval handle's (`MixingStyleEncoder.hip_encoder()`): the parameters are constants on this path."""
+    last_timing = None
+
+    @staticmethod
+    def forward(ctx, enc, logmel, feats):
+        B, _, M, Fr = logmel.shape
+        _, t, ws = enc.forward_frozen(logmel, feats, head=False)
+        ctx.enc, ctx.dims = enc, (B, Fr)
+        ctx.save_for_backward(ws)
+        return t["pool_in"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dpool_in):
+        enc, (B, Fr) = ctx.enc, ctx.dims
+        ws, = ctx.saved_tensors
+        marks = []
+
+        def mark(name):   # MST_TRAIN_TIMING=1: per-section GPU times of the last backward in _HipFrozenTrunk.last_timing
+            if _TRAIN_TIMING:
+                e = torch.cuda.Event(enable_timing=True)
+                e.record()
+                marks.append((name, e))
+        mark("start")
+        dy2 = enc.frozen_backward_apply(2, dpool_in, B, Fr, ws)
+        mark("apply_bwd2")
+        dp1 = enc.conv2_dgrad(dy2, B, Fr)
+        mark("conv2_dgrad")
+        dy1 = enc.frozen_backward_apply(1, dp1, B, Fr, ws)
+        mark("apply_bwd1")
+        dlm = enc.conv1_dgrad(dy1, B, Fr, ws)
+        mark("conv1_dgrad")
+        if _TRAIN_TIMING:
+            torch.cuda.synchronize()
+            _HipFrozenTrunk.last_timing = {b[0]: round(a[1].elapsed_time(b[1]), 3) for a, b in zip(marks[:-1], marks[1:])}
+        return None, dlm, None
+
+
 def _seed64():
     """A 62-bit seed from torch's CPU generator (reproducible under torch.manual_seed; no device work)."""
     return int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -924,6 +1039,12 @@ class MixingStyleEncoder(nn.Module):
         #   "torch"        = explicit opt-in: everything on PyTorch-ROCm autograd (BASELINE configs[1] / A-B comparisons)
         #   "hip-or-torch" = explicit opt-in: as "hip", but a refused call warns once per reason and runs on PyTorch-ROCm autograd
         self.train_backend = "hip"
+        # gradient to the INPUT (log-mel / waveform) through a frozen encoder in eval mode -- the style term of the style-transfer
+        # trainer: "none" (default) = encoder_backend "hip" has none (a stem that requires grad raises and names
+        # encoder_backend="torch"); "hip" = trunk and head, forward and backward, in libmst.so (_HipFrozenTrunk, _HipHead) when
+        # encoder_backend == "hip" and the module is in eval mode with every parameter frozen -- a call this path cannot take
+        # raises RuntimeError naming the reason
+        self.input_grad_backend = "none"
         # precision of the hand-written training trunk: "fp32" (exact), "f16" (float16 operands, fp32 accumulation:
         # the reference's --use_amp arithmetic, see include/mst.h mst_encoder_set_train_precision), "f16x3" (the same
         # kernels with 3-term split-precision operands: fp32-equivalent), or "auto" = f16 inside `torch.autocast(dtype=float16)`
@@ -1127,10 +1248,57 @@ class MixingStyleEncoder(nn.Module):
         return self._hip_trunk_refusal_for(logmel.frames if cm else logmel.shape[-1], (logmel.data if cm else logmel).is_cuda,
                                            torch.float32 if cm else logmel.dtype)
 
+    def _frozen_refusal(self, frames, on_gpu, dtype, mixing_features, features_follow=False):
+        """Why the hand-written frozen-encoder path (input_grad_backend = "hip") cannot take this call (None = it can).
+        features_follow: `forward` moves the mixing features to the log-mel's device itself."""
+        ae = self.audio_encoder
+        if self.training:
+            return "the module is in training mode; the frozen path is eval-mode BatchNorm without Dropout: call model.eval()"
+        live = [n for n, q in self.named_parameters() if q.requires_grad]
+        if live:
+            return (f"{len(live)} encoder parameters require grad (first: {live[0]}); this path differentiates the input only: "
+                    "freeze them with requires_grad_(False)")
+        if mixing_features.requires_grad:
+            return "mixing_features requires grad; the mixing features are constants on this path: detach them"
+        if not on_gpu or not (mixing_features.is_cuda or features_follow):
+            return "non-CUDA tensors: libmst kernels need CUDA (HIP) tensors and there is no CPU fallback"
+        if dtype != torch.float32 or mixing_features.dtype != torch.float32 or self.film_encoder.film_head.weight.dtype != torch.float32:
+            return (f"non-fp32 tensors (input {dtype}, mixing_features {mixing_features.dtype}, parameters "
+                    f"{self.film_encoder.film_head.weight.dtype}); the frozen path is fp32")
+        if self.conv1_precision != "fp32":
+            return f"conv1_precision='{self.conv1_precision}'; the frozen path is exact fp32: set conv1_precision='fp32'"
+        if ae.split_size // 10 not in (1, 2):
+            return f"split_size={ae.split_size}: the frozen-encoder kernels cover first-pool heights 1 and 2 (split_size // 10 in (1, 2))"
+        if frames < 20:
+            return f"{frames} frames < 20"
+        if not self._small_nets_in_hip(mixing_features, frames // 20):
+            return ("the attention head is outside the hand-written head kernels' limits (small_nets_backend='hip', attention hidden "
+                    "<= 256, pooled channels <= 3072, pooled frames <= 2048)")
+        return None
+
+    def _require_frozen_path(self, frames, on_gpu, dtype, mixing_features, features_follow=False):
+        why = self._frozen_refusal(frames, on_gpu, dtype, mixing_features, features_follow)
+        if why:
+            raise RuntimeError("MixingStyleEncoder.input_grad_backend='hip': the hand-written frozen-encoder path cannot take this call "
+                               f"({why}); encoder_backend=\"torch\" runs the conv trunk on PyTorch-ROCm autograd instead")
+
+    def _forward_frozen_hip(self, logmel, mixing_features):
+        """Frozen encoder with the gradient to the log-mel: trunk (_HipFrozenTrunk) and head (_HipHead, no Dropout) in libmst.so."""
+        self._require_frozen_path(logmel.shape[-1], logmel.is_cuda, logmel.dtype, mixing_features)
+        ap = self.audio_encoder.attention_pooling
+        pool_in = _HipFrozenTrunk.apply(self.hip_encoder(), logmel, mixing_features)
+        return _HipHead.apply(pool_in, 0.0, 0.0, ap.attention[0].weight, ap.attention[0].bias, ap.attention[2].weight,
+                              ap.attention[2].bias, ap.projection[0].weight, ap.projection[0].bias)
+
     def forward_from_logmel(self, logmel, mixing_features):
         if self.train_backend not in self._HIP_TRAIN_BACKENDS + ("torch",):
             raise ValueError("train_backend must be 'hip' (default; alias 'hip-strict'), 'torch' or 'hip-or-torch'")
+        if self.input_grad_backend not in ("none", "hip"):
+            raise ValueError("input_grad_backend must be 'none' (default) or 'hip'")
         auto = self._needs_autograd(mixing_features)
+        if self.input_grad_backend == "hip" and self.encoder_backend == "hip" and torch.is_grad_enabled() and \
+                torch.is_tensor(logmel) and logmel.requires_grad and not (self.training and auto and self.train_backend == "torch"):
+            return self._forward_frozen_hip(logmel, mixing_features)
         hip_train = self.encoder_backend == "hip" and self.training and auto and self.train_backend in self._HIP_TRAIN_BACKENDS
         if hip_train:   # decided BEFORE any layout conversion, so that a refusal names its reason
             why = self._hip_trunk_refusal(logmel)
@@ -1191,10 +1359,16 @@ class MixingStyleEncoder(nn.Module):
             # the style term of the style-transfer trainer (src/train_style_transfer.py:192-224): the gradient of the embedding to
             # the WAVEFORM.  Stage A forward and backward run in HIP (_LogMelHip); the conv trunk, FiLM and the head on
             # PyTorch-ROCm autograd.  The mixing features of the same launch condition the encoder as constants.
+            # With input_grad_backend = "hip" (and encoder_backend = "hip", model.eval(), frozen parameters) the trunk and the
+            # head run in libmst.so too (_HipFrozenTrunk, _HipHead): forward_from_logmel takes the log-mel that requires grad.
             if not (self.encoder_backend == "torch" or (self.training and auto and self.train_backend == "torch")):
-                raise RuntimeError("MixingStyleEncoder: a stem requires grad, but the hand-written HIP trunk (encoder_backend='hip') "
-                                   "has no gradient to its input yet; encoder_backend=\"torch\" runs stage A forward and backward in "
-                                   "HIP and the conv trunk on PyTorch-ROCm autograd (detach the stems if no waveform gradient is wanted)")
+                if self.input_grad_backend != "hip":
+                    raise RuntimeError("MixingStyleEncoder: a stem requires grad, but the hand-written HIP trunk (encoder_backend='hip') "
+                                       "gives no gradient to its input by default; encoder_backend=\"torch\" runs stage A forward and "
+                                       "backward in HIP and the conv trunk on PyTorch-ROCm autograd, input_grad_backend=\"hip\" runs the "
+                                       "frozen encoder's input gradient in HIP as well (detach the stems if no waveform gradient is wanted)")
+                first = next(iter(stems_dict.values()))
+                self._require_frozen_path(1 + first.shape[-1] // pre.hop_length, first.is_cuda, first.dtype, mixing_features, True)
             logmel, feats = pre.forward_with_grad(stems_dict, plan, has_feats)
         else:
             with torch.no_grad():
