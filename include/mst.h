@@ -267,8 +267,8 @@ int mst_encoder_set_train_precision(mst_encoder* enc, int mode);
 
 /* Refresh the convolution / BatchNorm parameters of the TRAINING kernels from device tensors (concatenated over the
  * sub-bands, reference state_dict shapes) -- once per optimizer step; re-swizzles the MFMA weight fragments on the
- * device.  The eval-mode constants (folded running statistics, f16 fragments) are NOT refreshed: create a new
- * encoder for evaluation after training.                                                                         */
+ * device.  The eval-only tables (folded running statistics, FiLM / pooling-head weights) are NOT refreshed: call
+ * mst_encoder_update_params before evaluating after training.                                                    */
 int mst_encoder_update_trunk_params(mst_encoder* enc, const float* conv1_w, const float* conv1_b, const float* bn1_w,
                                     const float* bn1_b, const float* conv2_w, const float* conv2_b,
                                     const float* bn2_w, const float* bn2_b, void* stream);
@@ -286,7 +286,8 @@ int mst_encoder_train_update_running_stats(const mst_encoder* enc, int layer, in
  * optimizer steps (src/train.py:388-427 follows :292-296): `w` has mst_encoder_create's fields, but every pointer is a DEVICE
  * tensor in state_dict layout (the sub-band tensors stacked over the bands).  Fragment swizzles, the eval BatchNorm fold, the
  * float16 fragments with their power-of-two pre-scales, transposes and copies all run as kernels on `stream`: no host
- * round trip, no synchronisation, no allocation after the first call.  The configuration (shapes) must be the one the
+ * round trip, no synchronisation, no allocation.  mst_encoder_create runs this same call on device copies of its host
+ * arrays, so a refreshed handle holds the bits a fresh one would.  The configuration (shapes) must be the one the
  * encoder was created with.                                                                                           */
 int mst_encoder_update_params(mst_encoder* enc, const mst_encoder_weights* device_weights, void* stream);
 

@@ -9,7 +9,7 @@
 // a wave tile is chosen so that every max-pool window lies in the accumulator registers of ONE lane: BN(eval),
 // FiLM, ReLU and the max-pool run in registers and only pooled activations reach HBM.
 //   * one workgroup = 8 waves (2 per SIMD), persistent over "sets" of 8 wave tiles of one sub-band;
-//   * weights stream through LDS in chunks of 4 input channels x 49 taps, pre-swizzled on the host into MFMA
+//   * weights stream through LDS in chunks of 4 input channels x 49 taps, pre-swizzled (conv_fragments_kernel) into MFMA
 //     B-fragment order (one conflict-free ds_read_b32 per fragment);
 //   * each wave owns a private LDS patch (4 channels x (rows+6) x (cols+6)) of its tile: no inter-wave
 //     hand-off except the shared weight chunk (one barrier per chunk);
@@ -1633,15 +1633,9 @@ typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ _Float16 to_f16_sat(float v) {
   return (_Float16)(__builtin_isfinite(v) ? fminf(fmaxf(v, -65504.f), 65504.f) : v);
 }
-// weight pre-scale of the f16 fragments: an exact power of two per (band, output channel), chosen on the host so that the
-// filter's largest |w| lands in [2^13, 2^14) -- wl = w - wh stays a normal f16 whatever the weights' magnitude -- and
+// weight pre-scale of the f16 fragments: an exact power of two per (band, output channel), chosen by f16_wstats_kernel so that
+// the filter's largest |w| lands in [2^13, 2^14) -- wl = w - wh stays a normal f16 whatever the weights' magnitude -- and
 // folded back per channel in the epilogue (ConvParams::f16_winv)
-__host__ inline int f16_weight_exponent(float maxabs) {
-  if (!(maxabs > 0.f) || !(maxabs < INFINITY)) return 10;
-  int ex;
-  (void)frexpf(maxabs, &ex);   // maxabs in [2^(ex-1), 2^ex)
-  return std::max(-100, std::min(100, 14 - ex));
-}
 constexpr int kF16Steps = 13;         // ceil(49 taps / 4)
 
 // TERMS = 3: split precision (fp32-equivalent, see above).  TERMS = 1: plain f16 operands (`x ~ xh`, `w ~ wh`), fp32
@@ -2732,7 +2726,7 @@ void launch_proj(const ProjParams& pj, hipStream_t st) {
 // (split_size >= 30: SUB = split_size // 10 >= 3, src/model.py:111-117).  Coverage of the reference's geometry, not the fast
 // path: fp32 FMAs on the vector unit, one workgroup = (clip, band, 8 pooled columns) holding the band's 392 x 32 weights and
 // the whole (split + 6) x 46 x 8 input patch in LDS; thread = (output channel, pooled column), walking the pooled rows.
-// Reads the weights from the MFMA fragment table (conv_fragments: [cin / 4][tap][n / 16][lane = 16 (cin % 4) + n % 16]).
+// Reads the weights from the MFMA fragment table (conv_fragments_kernel: [cin / 4][tap][n / 16][lane = 16 (cin % 4) + n % 16]).
 // ------------------------------------------------------------------------------------------
 constexpr int kGenCols = 8, kGenPC = 5 * kGenCols + 6;
 constexpr size_t conv1_generic_lds(int split_size) {   // the band's weights + the whole 8-channel input patch
@@ -2792,29 +2786,30 @@ __global__ __launch_bounds__(256) void conv1_generic_kernel(const ConvParams p, 
 struct mst_encoder {
   mst_encoder_config cfg{};
   int sub = 0, H1 = 0, FD = 0, C = 0;
+  std::vector<void*> owned;   // every device allocation of the handle (enc_alloc adds, mst_encoder_destroy frees)
   float *w1frag = nullptr, *w2frag = nullptr;
   float *s1 = nullptr, *t1 = nullptr, *s2 = nullptr, *t2 = nullptr;
   float *w0t = nullptr, *b0 = nullptr, *w3t = nullptr, *b3 = nullptr, *hwt = nullptr, *hb = nullptr;
   float *att0frag = nullptr, *att0_b = nullptr, *att2_w = nullptr, *projfrag = nullptr, *proj_b = nullptr;
   float* att2_b = nullptr;    // device [1]
   int num_cus = 256;
-  float *f16_wsc1e = nullptr, *f16_wsc2e = nullptr, *w2norm_e = nullptr;   // scratch of the device-side refresh (mst_encoder_update_params)
-  void* w1frag16 = nullptr;   // conv1 weights as f16 hi/lo MFMA B fragments (opt-in split-precision path)
-  void* w1frag16e = nullptr;  // the same weights in conv1_f16e_kernel's k order (14 steps: one tap column x four tap rows)
-  void* w2frag16 = nullptr;   // conv2 likewise: [band][4 chunks][13 steps][4 nt][hi/lo][lane][8]
+  _Float16* w1frag16 = nullptr;   // conv1 weights as f16 hi/lo MFMA B fragments (opt-in split-precision path)
+  _Float16* w1frag16e = nullptr;  // the same weights in conv1_f16e_kernel's k order (14 steps: one tap column x four tap rows)
+  _Float16* w2frag16 = nullptr;   // conv2 likewise: [band][4 chunks][13 steps][4 nt][hi/lo][lane][8]
+  float *f16_wsc1 = nullptr, *f16_wsc2 = nullptr;     // [nsub][32], [nsub][64]: pre-scale 2^k of the f16 weight fragments (scratch of their build)
+  float *f16_winv1 = nullptr, *f16_winv2 = nullptr;   // [nsub][32], [nsub][64]: its inverse, for the epilogues
   float* w1norm = nullptr;    // [nsub][32] L1 norm of every conv1 filter (range bound of the f16 path)
-  float *f16_winv1 = nullptr, *f16_winv2 = nullptr;   // [nsub][32], [nsub][64]: inverse pre-scale of the f16 weight fragments
+  float* w2norm = nullptr;    // [nsub][64] L1 norms of the conv2 filters (range bound of the stored f16 conv2 outputs, training mode 1)
   int conv1_f16x3 = 0;        // 0 exact fp32, 1 conv1 f16x3, 2 conv1 + conv2 f16x3, 3 conv1 + conv2 plain f16 (amp)
   // un-folded parameters for the training forward (batch-statistics BatchNorm)
   float *c1b = nullptr, *bn1w = nullptr, *bn1b = nullptr, *c2b = nullptr, *bn2w = nullptr, *bn2b = nullptr;
   float* w2dfrag = nullptr;   // conv2 input-gradient weight fragments [nsub][16][WBP] (refreshed by update_trunk_params)
   float* w1dfrag = nullptr;   // conv1 input-gradient weight fragments [nsub][8][WBP] (likewise)
   float* zero_bias = nullptr; // [nsub][64] zeros: the frozen forward's raw kernels add no bias (the eval affines carry it)
-  // f16-operand training (mst_encoder_set_train_precision): fragments and pre-scales rebuilt on the device every step
+  // f16-operand training (mst_encoder_set_train_precision, which allocates these three): rebuilt on the device every step
   int train_f16 = 0;
-  void* w2dfrag16 = nullptr;  // conv2 input-gradient fragments, hi only: [nsub][8 chunks][13 steps][2 nt][lane][8]
-  float *f16_wsc1 = nullptr, *f16_wsc2 = nullptr, *f16_wsc2d = nullptr, *f16_winv2d = nullptr;   // pre-scales 2^k and the dgrad inverse
-  float* w2norm = nullptr;    // [nsub][64] L1 norms of the conv2 filters (range bound of the stored f16 conv2 outputs, mode 1)
+  _Float16* w2dfrag16 = nullptr;  // conv2 input-gradient fragments, hi only: [nsub][8 chunks][13 steps][2 nt][lane][8]
+  float *f16_wsc2d = nullptr, *f16_winv2d = nullptr;   // [nsub][32]: their pre-scale 2^k and its inverse
 };
 
 namespace {
@@ -2856,27 +2851,15 @@ WsLayout ws_layout(const mst_encoder* e, int B, int frames) {
   return L;
 }
 
-std::vector<float> transpose(const float* w, int rows, int cols) {  // [rows][cols] -> [cols][rows]
-  std::vector<float> t((size_t)rows * cols);
-  for (int r = 0; r < rows; ++r)
-    for (int c = 0; c < cols; ++c) t[(size_t)c * rows + r] = w[(size_t)r * cols + c];
-  return t;
-}
-
-// conv weights [nsub][COUT][CIN][7][7] -> [nsub][CIN/4][WCHP] with chunk layout [tap][nt][lane]
-std::vector<float> conv_fragments(const float* w, int nsub, int cout, int cin, int wchp) {
-  const int nt = cout / 16, nch = cin / 4;
-  std::vector<float> f((size_t)nsub * nch * wchp, 0.f);
-  for (int b = 0; b < nsub; ++b)
-    for (int ch = 0; ch < nch; ++ch)
-      for (int tap = 0; tap < 49; ++tap)
-        for (int n = 0; n < nt; ++n)
-          for (int lane = 0; lane < 64; ++lane) {
-            const int co = n * 16 + (lane & 15), ci = 4 * ch + (lane >> 4);
-            f[((size_t)b * nch + ch) * wchp + ((size_t)tap * nt + n) * 64 + lane] =
-                w[(((size_t)b * cout + co) * cin + ci) * 49 + tap];
-          }
-  return f;
+// THE allocation of a device buffer the handle owns: n elements, zeroed on request, recorded in e->owned
+template <class T>
+int enc_alloc(mst_encoder* e, T** p, size_t n, bool zero = false) {
+  void* q = nullptr;
+  if (hipMalloc(&q, n * sizeof(T)) != hipSuccess) return mst::fail(MST_ENOMEM, "mst_encoder: hipMalloc(%zu B) failed", n * sizeof(T));
+  e->owned.push_back(q);
+  *p = static_cast<T*>(q);
+  if (zero) MST_HIP_CHECK(hipMemset(q, 0, n * sizeof(T)));
+  return MST_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3761,7 +3744,8 @@ __global__ void det_to_float_kernel(const mst::DetAcc* acc, float* out, long lon
   if (i < n) out[i] = (float)(mst::det_get(acc[i]) * u);
 }
 
-// conv weights [nsub][COUT][CIN][49] (device) -> MFMA B-fragment chunks, same layout as conv_fragments() builds on the host
+// conv weights [nsub][COUT][CIN][49] (device) -> MFMA B-fragment chunks [nsub][CIN/4][wchp], chunk layout [tap][nt][lane]:
+// lane (n, kq) of tap, tile nt holds w[co = 16 nt + n][ci = 4 chunk + kq][tap]; the pitch's padding is not written
 __global__ void conv_fragments_kernel(const float* w, float* f, int nsub, int cout, int cin, int wchp) {
   const int nt = cout / 16, nch = cin / 4;
   const long long total = (long long)nsub * nch * 49 * nt * 64;
@@ -3804,6 +3788,22 @@ hipError_t launch_dgrad_fragments(const mst_encoder* e, const float* conv1_w, co
                      ConvGeom<3, 2>::WBP);
   hipLaunchKernelGGL(dgrad_fragments_kernel, dim3((unsigned)((t1 + 255) / 256)), dim3(256), 0, st, conv1_w, e->w1dfrag, ns, 32, 8,
                      ConvGeom<5, 2>::WBP);
+  return hipGetLastError();
+}
+// float16 hi / lo fragments of conv1 and conv2 in the 13-step k order (eval modes 1-3 and f16 training read the same tables), with
+// their per-channel pre-scales, the inverses and the filters' L1 norms: the per-step trunk refresh (f16 training) and the refresh
+// of every table both build them here, never both in one call
+hipError_t launch_f16_forward_fragments(const mst_encoder* e, const float* conv1_w, const float* conv2_w, hipStream_t st) {
+  const int ns = e->cfg.n_subbands;
+  hipLaunchKernelGGL(f16_wstats_kernel, dim3(ns * 32), dim3(64), 0, st, conv1_w, 32, (long long)32 * 392, 392, 1, 0, 392,
+                     e->f16_wsc1, e->f16_winv1, e->w1norm);
+  hipLaunchKernelGGL(f16_wstats_kernel, dim3(ns * 64), dim3(64), 0, st, conv2_w, 64, (long long)64 * 1568, 1568, 1, 0, 1568,
+                     e->f16_wsc2, e->f16_winv2, e->w2norm);
+  const long long n1 = (long long)ns * 1 * kF16Steps * 2 * 512, n2 = (long long)ns * 4 * kF16Steps * 4 * 512;
+  hipLaunchKernelGGL(f16_fragments_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, st, conv1_w, e->f16_wsc1, e->w1frag16,
+                     ns, 32, 8, 2, 0);
+  hipLaunchKernelGGL(f16_fragments_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, conv2_w, e->f16_wsc2, e->w2frag16,
+                     ns, 64, 32, 2, 0);
   return hipGetLastError();
 }
 
@@ -3977,147 +3977,51 @@ int mst_encoder_create(mst_encoder** out, const mst_encoder_config* cfg, const m
               "floats + 10 KB <= 64 KB)", cfg->feature_dim, cfg->film_hidden);
   for (const float* const* q = &w->conv1_w; q <= &w->proj_b; ++q)
     MST_REQUIRE(*q != nullptr, "mst_encoder_create: NULL weight pointer");
+  const int H1 = cfg->split_size / sub, FD = H1 / 4, C = 64 * ns * FD;
+  const int H = cfg->film_hidden, Fd = cfg->feature_dim, A = cfg->attn_hidden, E = cfg->embed_dim;
+  MST_REQUIRE(FD >= 1 && C % 4 == 0, "mst_encoder_create: bad pooled geometry");
+  MST_REQUIRE(E % 16 == 0, "mst_encoder_create: embed_dim must be a multiple of 16 (got %d)", E);
   mst_encoder* e = new mst_encoder();
   e->cfg = *cfg;
-  e->sub = sub;
-  e->H1 = cfg->split_size / sub;
-  e->FD = e->H1 / 4;
-  e->C = 64 * ns * e->FD;
-  MST_REQUIRE(e->FD >= 1 && e->C % 4 == 0, "mst_encoder_create: bad pooled geometry");
+  e->sub = sub, e->H1 = H1, e->FD = FD, e->C = C;
   int dev = 0;
   hipDeviceProp_t prop;
   if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
     e->num_cus = prop.multiProcessorCount;
-  const int H = cfg->film_hidden, Fd = cfg->feature_dim, A = cfg->attn_hidden, E = cfg->embed_dim, C = e->C;
-  // BN(eval) folded with the conv bias, in double
-  auto fold = [&](const float* cb, const float* bw, const float* bb, const float* mean, const float* var, int n,
-                  std::vector<float>& s, std::vector<float>& t) {
-    s.resize(n), t.resize(n);
-    for (int i = 0; i < n; ++i) {
-      const double sc = (double)bw[i] / std::sqrt((double)var[i] + (double)cfg->bn_eps);
-      s[i] = (float)sc;
-      t[i] = (float)(sc * ((double)cb[i] - (double)mean[i]) + (double)bb[i]);
-    }
-  };
-  std::vector<float> s1, t1, s2, t2;
-  fold(w->conv1_b, w->bn1_w, w->bn1_b, w->bn1_mean, w->bn1_var, ns * 32, s1, t1);
-  fold(w->conv2_b, w->bn2_w, w->bn2_b, w->bn2_mean, w->bn2_var, ns * 64, s2, t2);
-  auto f1 = conv_fragments(w->conv1_w, ns, 32, 8, ConvGeom<1, 2>::WBP);   // pitch does not depend on SUB
-  auto f2 = conv_fragments(w->conv2_w, ns, 64, 32, ConvGeom<2, 2>::WBP);
-  auto w0t = transpose(w->mlp0_w, H, Fd), w3t = transpose(w->mlp3_w, H, H), hwt = transpose(w->head_w, ns * 192, H);
-  MST_REQUIRE(E % 16 == 0, "mst_encoder_create: embed_dim must be a multiple of 16 (got %d)", E);
-  std::vector<float> pfrag((size_t)(C / 4) * (E / 16) * 64);
-  for (int s = 0; s < C / 4; ++s)
-    for (int n = 0; n < E / 16; ++n)
-      for (int lane = 0; lane < 64; ++lane)
-        pfrag[((size_t)s * (E / 16) + n) * 64 + lane] = w->proj_w[(size_t)(n * 16 + (lane & 15)) * C + 4 * s + (lane >> 4)];
-  std::vector<float> af((size_t)(C / 4) * (A / 16) * 64);
-  for (int s = 0; s < C / 4; ++s)
-    for (int n = 0; n < A / 16; ++n)
-      for (int lane = 0; lane < 64; ++lane)
-        af[((size_t)s * (A / 16) + n) * 64 + lane] = w->att0_w[(size_t)(n * 16 + (lane & 15)) * C + 4 * s + (lane >> 4)];
-  // per-(band, output channel) power-of-two pre-scale of the f16 weight fragments, and its inverse for the epilogues
-  std::vector<int> wex1((size_t)ns * 32), wex2((size_t)ns * 64);
-  std::vector<float> winv1((size_t)ns * 32), winv2((size_t)ns * 64);
-  for (int b = 0; b < ns; ++b) {
-    for (int co = 0; co < 32; ++co) {
-      float mx = 0.f;
-      for (int i = 0; i < 392; ++i) mx = std::max(mx, fabsf(w->conv1_w[((size_t)b * 32 + co) * 392 + i]));
-      wex1[(size_t)b * 32 + co] = f16_weight_exponent(mx);
-      winv1[(size_t)b * 32 + co] = ldexpf(1.0f, -wex1[(size_t)b * 32 + co]);
-    }
-    for (int co = 0; co < 64; ++co) {
-      float mx = 0.f;
-      for (int i = 0; i < 1568; ++i) mx = std::max(mx, fabsf(w->conv2_w[((size_t)b * 64 + co) * 1568 + i]));
-      wex2[(size_t)b * 64 + co] = f16_weight_exponent(mx);
-      winv2[(size_t)b * 64 + co] = ldexpf(1.0f, -wex2[(size_t)b * 64 + co]);
-    }
+  // every table of the handle (mst_encoder_set_train_precision adds the f16 input-gradient fragments).  Zeroed: the conv fragments,
+  // whose pitch (ConvGeom<..>::WBP, the same for every SUB) exceeds what their builders write, and the bias nobody writes
+  const size_t n32 = (size_t)ns * 32, n64 = (size_t)ns * 64, f16blk = 2 * 2 * 64 * 8;   // [nt][hi/lo][lane][8] of one conv1 k-step
+  const struct { float** p; size_t n; bool zero; } tables[] = {
+      {&e->w1frag, (size_t)ns * 2 * ConvGeom<1, 2>::WBP, true}, {&e->w2frag, (size_t)ns * 8 * ConvGeom<2, 2>::WBP, true},
+      {&e->w2dfrag, (size_t)ns * 16 * ConvGeom<3, 2>::WBP, true}, {&e->w1dfrag, (size_t)ns * 8 * ConvGeom<5, 2>::WBP, true},
+      {&e->zero_bias, n64, true},
+      {&e->s1, n32}, {&e->t1, n32}, {&e->c1b, n32}, {&e->bn1w, n32}, {&e->bn1b, n32},
+      {&e->s2, n64}, {&e->t2, n64}, {&e->c2b, n64}, {&e->bn2w, n64}, {&e->bn2b, n64},
+      {&e->f16_wsc1, n32}, {&e->f16_winv1, n32}, {&e->w1norm, n32}, {&e->f16_wsc2, n64}, {&e->f16_winv2, n64}, {&e->w2norm, n64},
+      {&e->w0t, (size_t)H * Fd}, {&e->b0, (size_t)H}, {&e->w3t, (size_t)H * H}, {&e->b3, (size_t)H},
+      {&e->hwt, (size_t)ns * 192 * H}, {&e->hb, (size_t)ns * 192},
+      {&e->att0frag, (size_t)A * C}, {&e->att0_b, (size_t)A}, {&e->att2_w, (size_t)A}, {&e->att2_b, 1},
+      {&e->projfrag, (size_t)E * C}, {&e->proj_b, (size_t)E}};
+  int rc = MST_OK;
+  for (const auto& t : tables)
+    if (!rc) rc = enc_alloc(e, t.p, t.n, t.zero);
+  if (!rc) rc = enc_alloc(e, &e->w1frag16, (size_t)ns * kF16Steps * f16blk);
+  if (!rc) rc = enc_alloc(e, &e->w1frag16e, (size_t)ns * kF16StepsE * f16blk);
+  if (!rc) rc = enc_alloc(e, &e->w2frag16, (size_t)ns * 4 * kF16Steps * 2 * f16blk);
+  // stage the caller's host arrays on the device (element counts in mst_encoder_weights' field order) and run THE refresh
+  const size_t count[] = {n32 * 392, n32, n32, n32, n32, n32, n64 * 1568, n64, n64, n64, n64, n64,
+                          (size_t)H * Fd, (size_t)H, (size_t)H * H, (size_t)H, (size_t)ns * 192 * H, (size_t)ns * 192,
+                          (size_t)A * C, (size_t)A, (size_t)A, 1, (size_t)E * C, (size_t)E};
+  constexpr int kFields = sizeof(count) / sizeof(count[0]);
+  static_assert(sizeof(mst_encoder_weights) == kFields * sizeof(const float*), "one count per field of mst_encoder_weights");
+  mst::DevBuf<float> stage[kFields];
+  mst_encoder_weights dw{};
+  for (int i = 0; i < kFields && !rc; ++i) {
+    rc = stage[i].upload((&w->conv1_w)[i], count[i]);
+    (&dw.conv1_w)[i] = stage[i].get();
   }
-  // conv1 weights, f16 hi/lo split of (2^e * w): [band][step][nt][hi/lo][lane][8 channels]
-  std::vector<_Float16> f16((size_t)ns * kF16Steps * 2 * 2 * 64 * 8);
-  for (int b = 0; b < ns; ++b)
-    for (int st = 0; st < kF16Steps; ++st)
-      for (int n = 0; n < 2; ++n)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int j = 0; j < 8; ++j) {
-            const int tap = 4 * st + (lane >> 4), co = n * 16 + (lane & 15);
-            const float wv = tap < 49 ? ldexpf(w->conv1_w[(((size_t)b * 32 + co) * 8 + j) * 49 + tap], wex1[(size_t)b * 32 + co]) : 0.f;
-            const _Float16 h = (_Float16)wv;
-            const size_t base = ((((size_t)b * kF16Steps + st) * 2 + n) * 2) * 64 * 8;
-            f16[base + (size_t)lane * 8 + j] = h;
-            f16[base + 64 * 8 + (size_t)lane * 8 + j] = (_Float16)(wv - (float)h);
-          }
-  // ... and in the k order of conv1_f16e_kernel: step = (tap column, upper / lower tap rows), k-group kq -> tap row (0, 2, 1, 3)
-  std::vector<_Float16> f16e((size_t)ns * kF16StepsE * 2 * 2 * 64 * 8);
-  for (int b = 0; b < ns; ++b)
-    for (int st = 0; st < kF16StepsE; ++st)
-      for (int n = 0; n < 2; ++n)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int j = 0; j < 8; ++j) {
-            const int kq = lane >> 4, tr = 4 * (st & 1) + (((kq & 1) << 1) | (kq >> 1)), tc = st >> 1, co = n * 16 + (lane & 15);
-            const float wv = tr < 7 ? ldexpf(w->conv1_w[(((size_t)b * 32 + co) * 8 + j) * 49 + tr * 7 + tc], wex1[(size_t)b * 32 + co]) : 0.f;
-            const _Float16 h = (_Float16)wv;
-            const size_t base = ((((size_t)b * kF16StepsE + st) * 2 + n) * 2) * 64 * 8;
-            f16e[base + (size_t)lane * 8 + j] = h;
-            f16e[base + 64 * 8 + (size_t)lane * 8 + j] = (_Float16)(wv - (float)h);
-          }
-  std::vector<_Float16> g16((size_t)ns * 4 * kF16Steps * 4 * 2 * 64 * 8);
-  for (int b = 0; b < ns; ++b)
-    for (int ck = 0; ck < 4; ++ck)
-      for (int st = 0; st < kF16Steps; ++st)
-        for (int n = 0; n < 4; ++n)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 8; ++j) {
-              const int tap = 4 * st + (lane >> 4), co = n * 16 + (lane & 15), ci = ck * 8 + j;
-              const float wv = tap < 49 ? ldexpf(w->conv2_w[(((size_t)b * 64 + co) * 32 + ci) * 49 + tap], wex2[(size_t)b * 64 + co]) : 0.f;
-              const _Float16 h = (_Float16)wv;
-              const size_t base = (((((size_t)b * 4 + ck) * kF16Steps + st) * 4 + n) * 2) * 64 * 8;
-              g16[base + (size_t)lane * 8 + j] = h;
-              g16[base + 64 * 8 + (size_t)lane * 8 + j] = (_Float16)(wv - (float)h);
-            }
-  std::vector<float> w1n((size_t)ns * 32);   // L1 norms of the conv1 filters, with a margin for the hi/lo rounding
-  for (int b = 0; b < ns; ++b)
-    for (int co = 0; co < 32; ++co) {
-      double a = 0.0;
-      for (int i = 0; i < 8 * 49; ++i) a += fabs((double)w->conv1_w[((size_t)b * 32 + co) * 392 + i]);
-      w1n[(size_t)b * 32 + co] = (float)(a * 1.001);
-    }
-  int rc = 0;
-  {
-    _Float16 *d16 = nullptr, *e16 = nullptr, *d16e = nullptr;
-    rc = mst::upload(&d16, f16.data(), f16.size());
-    if (!rc) rc = mst::upload(&e16, g16.data(), g16.size());
-    if (!rc) rc = mst::upload(&d16e, f16e.data(), f16e.size());
-    e->w1frag16 = d16, e->w2frag16 = e16, e->w1frag16e = d16e;
-  }
-#define UP(dst, vec) if (!rc) rc = mst::upload(&e->dst, (vec).data(), (vec).size())
-#define UPP(dst, ptr, n) if (!rc) rc = mst::upload(&e->dst, ptr, (size_t)(n))
-  UP(w1norm, w1n); UP(f16_winv1, winv1); UP(f16_winv2, winv2);
-  UP(w1frag, f1); UP(w2frag, f2); UP(s1, s1); UP(t1, t1); UP(s2, s2); UP(t2, t2);
-  UP(w0t, w0t); UP(w3t, w3t); UP(hwt, hwt); UP(projfrag, pfrag); UP(att0frag, af);
-  UPP(b0, w->mlp0_b, H); UPP(b3, w->mlp3_b, H); UPP(hb, w->head_b, ns * 192);
-  UPP(att0_b, w->att0_b, A); UPP(att2_w, w->att2_w, A); UPP(proj_b, w->proj_b, E); UPP(att2_b, w->att2_b, 1);
-  UPP(c1b, w->conv1_b, ns * 32); UPP(bn1w, w->bn1_w, ns * 32); UPP(bn1b, w->bn1_b, ns * 32);
-  UPP(c2b, w->conv2_b, ns * 64); UPP(bn2w, w->bn2_w, ns * 64); UPP(bn2b, w->bn2_b, ns * 64);
-  if (!rc) {   // input-gradient fragments of conv2 and conv1, built on the device from temporary copies of the weights
-    float *tmp2 = nullptr, *tmp1 = nullptr;
-    const size_t n2 = (size_t)ns * 16 * ConvGeom<3, 2>::WBP, n1 = (size_t)ns * 8 * ConvGeom<5, 2>::WBP;
-    rc = mst::upload(&tmp2, w->conv2_w, (size_t)ns * 64 * 32 * 49);
-    if (!rc) rc = mst::upload(&tmp1, w->conv1_w, (size_t)ns * 32 * 8 * 49);
-    if (!rc && (hipMalloc(&e->w2dfrag, n2 * sizeof(float)) != hipSuccess || hipMalloc(&e->w1dfrag, n1 * sizeof(float)) != hipSuccess ||
-                hipMalloc(&e->zero_bias, (size_t)ns * 64 * sizeof(float)) != hipSuccess))
-      rc = MST_ENOMEM;
-    if (!rc) {
-      (void)hipMemset(e->w2dfrag, 0, n2 * sizeof(float));
-      (void)hipMemset(e->w1dfrag, 0, n1 * sizeof(float));
-      (void)hipMemset(e->zero_bias, 0, (size_t)ns * 64 * sizeof(float));
-      if (launch_dgrad_fragments(e, tmp1, tmp2, 0) != hipSuccess) rc = MST_EHIP;
-      (void)hipDeviceSynchronize();
-    }
-    (void)hipFree(tmp2), (void)hipFree(tmp1);
-  }
-#undef UP
-#undef UPP
+  if (!rc) rc = mst_encoder_update_params(e, &dw, nullptr);
+  if (!rc && hipDeviceSynchronize() != hipSuccess) rc = mst::fail(MST_EHIP, "mst_encoder_create: building the tables failed");
   if (rc) {
     mst_encoder_destroy(e);
     return rc;
@@ -4128,16 +4032,7 @@ int mst_encoder_create(mst_encoder** out, const mst_encoder_config* cfg, const m
 
 void mst_encoder_destroy(mst_encoder* e) {
   if (!e) return;
-  float* ptrs[] = {e->w1frag, e->w2frag, e->s1, e->t1, e->s2, e->t2, e->w0t, e->b0, e->w3t, e->b3, e->hwt,
-                   e->hb, e->att0frag, e->att0_b, e->att2_w, e->projfrag, e->proj_b, e->c1b, e->bn1w, e->bn1b, e->c2b,
-                   e->bn2w, e->bn2b, e->w2dfrag, e->w1dfrag, e->zero_bias, e->att2_b, e->f16_wsc1e, e->f16_wsc2e, e->w2norm_e};
-  for (float* q : ptrs) (void)hipFree(q);
-  (void)hipFree(e->w1frag16), (void)hipFree(e->w1frag16e);
-  (void)hipFree(e->w1norm), (void)hipFree(e->f16_winv1), (void)hipFree(e->f16_winv2);
-  (void)hipFree(e->w2frag16);
-  (void)hipFree(e->w2dfrag16);
-  (void)hipFree(e->f16_wsc1), (void)hipFree(e->f16_wsc2), (void)hipFree(e->f16_wsc2d), (void)hipFree(e->f16_winv2d);
-  (void)hipFree(e->w2norm);
+  for (void* q : e->owned) (void)hipFree(q);
   delete e;
 }
 
@@ -4153,13 +4048,12 @@ int mst_encoder_set_train_precision(mst_encoder* e, int f16_operands) {
   MST_REQUIRE(e, "mst_encoder_set_train_precision: NULL encoder");
   MST_REQUIRE(f16_operands == 0 || ((f16_operands == 1 || f16_operands == 2) && (e->sub == 2 || e->cfg.split_size % 2 == 0)),
               "mst_encoder_set_train_precision: modes 1 (f16 operands) and 2 (split precision) need 2-row conv1 tiles (20-mel sub-bands, or an even split_size below 20)");
-  if (f16_operands && !e->w2dfrag16) {
-    const int ns = e->cfg.n_subbands;
-    bool ok = hipMalloc(&e->w2dfrag16, (size_t)ns * 8 * kF16Steps * 2 * 2 * 64 * 8 * sizeof(_Float16)) == hipSuccess;   // room for hi + lo
-    ok = ok && hipMalloc(&e->f16_wsc1, (size_t)ns * 32 * 4) == hipSuccess && hipMalloc(&e->f16_wsc2, (size_t)ns * 64 * 4) == hipSuccess;
-    ok = ok && hipMalloc(&e->f16_wsc2d, (size_t)ns * 32 * 4) == hipSuccess && hipMalloc(&e->f16_winv2d, (size_t)ns * 32 * 4) == hipSuccess;
-    ok = ok && hipMalloc(&e->w2norm, (size_t)ns * 64 * 4) == hipSuccess;
-    if (!ok) return mst::fail(MST_ENOMEM, "mst_encoder_set_train_precision: out of device memory");
+  if (f16_operands && !e->w2dfrag16) {   // first use: megabytes that only f16 training reads (the fragments last: they are the guard)
+    const size_t ns = e->cfg.n_subbands;
+    int rc = enc_alloc(e, &e->f16_wsc2d, ns * 32);
+    if (!rc) rc = enc_alloc(e, &e->f16_winv2d, ns * 32);
+    if (!rc) rc = enc_alloc(e, &e->w2dfrag16, ns * 8 * kF16Steps * 2 * 2 * 64 * 8);   // room for hi + lo
+    if (rc) return rc;
   }
   e->train_f16 = f16_operands;
   return MST_OK;
@@ -4809,20 +4703,12 @@ int mst_encoder_update_trunk_params(mst_encoder* e, const float* conv1_w, const 
     MST_HIP_CHECK(launch_dgrad_fragments(e, conv1_w, conv2_w, st));
   }
   if (train_fwd16(e)) {   // f16 fragments of the new weights: per-channel power-of-two pre-scale, then hi/lo (forward) / hi (dgrad)
-    hipLaunchKernelGGL(f16_wstats_kernel, dim3(ns * 32), dim3(64), 0, st, conv1_w, 32, (long long)32 * 392, 392, 1, 0, 392,
-                       e->f16_wsc1, e->f16_winv1, e->w1norm);
-    hipLaunchKernelGGL(f16_wstats_kernel, dim3(ns * 64), dim3(64), 0, st, conv2_w, 64, (long long)64 * 1568, 1568, 1, 0, 1568,
-                       e->f16_wsc2, e->f16_winv2, e->w2norm);
+    MST_HIP_CHECK(launch_f16_forward_fragments(e, conv1_w, conv2_w, st));
     hipLaunchKernelGGL(f16_wstats_kernel, dim3(ns * 32), dim3(64), 0, st, conv2_w, 32, (long long)64 * 1568, 49, 64, 1568, 49,
                        e->f16_wsc2d, e->f16_winv2d, static_cast<float*>(nullptr));
-    const long long n1 = (long long)ns * 1 * kF16Steps * 2 * 512, n2 = (long long)ns * 4 * kF16Steps * 4 * 512,
-                    n3 = (long long)ns * 8 * kF16Steps * 2 * 512;
-    hipLaunchKernelGGL(f16_fragments_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, st, conv1_w, e->f16_wsc1,
-                       reinterpret_cast<_Float16*>(e->w1frag16), ns, 32, 8, 2, 0);
-    hipLaunchKernelGGL(f16_fragments_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, conv2_w, e->f16_wsc2,
-                       reinterpret_cast<_Float16*>(e->w2frag16), ns, 64, 32, 2, 0);
-    hipLaunchKernelGGL(f16_fragments_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, conv2_w, e->f16_wsc2d,
-                       reinterpret_cast<_Float16*>(e->w2dfrag16), ns, 32, 64, e->train_f16 == 2 ? 2 : 1, 1);
+    const long long n3 = (long long)ns * 8 * kF16Steps * 2 * 512;
+    hipLaunchKernelGGL(f16_fragments_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, conv2_w, e->f16_wsc2d, e->w2dfrag16,
+                       ns, 32, 64, e->train_f16 == 2 ? 2 : 1, 1);
     MST_HIP_CHECK(hipGetLastError());
   }
   CopySix c6{{e->c1b, e->bn1w, e->bn1b, e->c2b, e->bn2w, e->bn2b}, {conv1_b, bn1_w, bn1_b, conv2_b, bn2_w, bn2_b},
@@ -4832,8 +4718,9 @@ int mst_encoder_update_trunk_params(mst_encoder* e, const float* conv1_w, const 
   return MST_OK;
 }
 
-// ---- device-side refresh of EVERY table of the encoder (eval and training) from device tensors in state_dict layout
-// BatchNorm(eval) folded with the convolution bias: y = s * conv + t  (as mst_encoder_create does on the host, in double)
+// ---- THE builder of EVERY table of the encoder (eval and training) from device tensors in state_dict layout: the refresh, and
+// what mst_encoder_create runs on staged copies of its host arrays.  Each layout is written down once, in its kernel.
+// BatchNorm(eval) folded with the convolution bias: y = s * conv + t  (in double)
 __global__ void bn_fold_eval_kernel(const float* cb, const float* bw, const float* bb, const float* mean, const float* var, int n,
                                     float eps, float* s, float* t) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -4892,23 +4779,11 @@ int mst_encoder_update_params(mst_encoder* e, const mst_encoder_weights* w, void
                      ns * 32, e->cfg.bn_eps, e->s1, e->t1);
   hipLaunchKernelGGL(bn_fold_eval_kernel, blocks(ns * 64), dim3(256), 0, st, w->conv2_b, w->bn2_w, w->bn2_b, w->bn2_mean, w->bn2_var,
                      ns * 64, e->cfg.bn_eps, e->s2, e->t2);
-  // eval-path float16 fragments (all three orders) with their per-channel power-of-two pre-scales and the filters' L1 norms
-  if (!e->f16_wsc1e) {
-    bool ok = hipMalloc(&e->f16_wsc1e, (size_t)ns * 32 * 4) == hipSuccess && hipMalloc(&e->f16_wsc2e, (size_t)ns * 64 * 4) == hipSuccess &&
-              hipMalloc(&e->w2norm_e, (size_t)ns * 64 * 4) == hipSuccess;
-    if (!ok) return mst::fail(MST_ENOMEM, "mst_encoder_update_params: out of device memory");
-  }
-  hipLaunchKernelGGL(f16_wstats_kernel, dim3(ns * 32), dim3(64), 0, st, w->conv1_w, 32, (long long)32 * 392, 392, 1, 0, 392,
-                     e->f16_wsc1e, e->f16_winv1, e->w1norm);
-  hipLaunchKernelGGL(f16_wstats_kernel, dim3(ns * 64), dim3(64), 0, st, w->conv2_w, 64, (long long)64 * 1568, 1568, 1, 0, 1568,
-                     e->f16_wsc2e, e->f16_winv2, e->w2norm_e);
-  const long long n1 = (long long)ns * 1 * kF16Steps * 2 * 512, n2 = (long long)ns * 4 * kF16Steps * 4 * 512,
-                  n1e = (long long)ns * kF16StepsE * 2 * 512;
-  hipLaunchKernelGGL(f16_fragments_kernel, blocks(n1), dim3(256), 0, st, w->conv1_w, e->f16_wsc1e, reinterpret_cast<_Float16*>(e->w1frag16),
-                     ns, 32, 8, 2, 0);
-  hipLaunchKernelGGL(f16_fragments_kernel, blocks(n2), dim3(256), 0, st, w->conv2_w, e->f16_wsc2e, reinterpret_cast<_Float16*>(e->w2frag16),
-                     ns, 64, 32, 2, 0);
-  hipLaunchKernelGGL(f16e_fragments_kernel, blocks(n1e), dim3(256), 0, st, w->conv1_w, e->f16_wsc1e, reinterpret_cast<_Float16*>(e->w1frag16e), ns);
+  // eval-path float16 fragments (all three orders) with their per-channel power-of-two pre-scales and the filters' L1 norms; in
+  // the f16 training modes the trunk refresh above has built the two 13-step orders already
+  if (!train_fwd16(e)) MST_HIP_CHECK(launch_f16_forward_fragments(e, w->conv1_w, w->conv2_w, st));
+  hipLaunchKernelGGL(f16e_fragments_kernel, blocks((long long)ns * kF16StepsE * 2 * 512), dim3(256), 0, st, w->conv1_w, e->f16_wsc1,
+                     e->w1frag16e, ns);
   // FiLM MLP (transposed weights), attention pooling head (fp32-MFMA B fragments), biases
   hipLaunchKernelGGL(transpose_kernel, blocks((long long)H * Fd), dim3(256), 0, st, w->mlp0_w, e->w0t, H, Fd);
   hipLaunchKernelGGL(transpose_kernel, blocks((long long)H * H), dim3(256), 0, st, w->mlp3_w, e->w3t, H, H);

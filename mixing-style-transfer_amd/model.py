@@ -289,26 +289,34 @@ class MixingFeatureEncoder(nn.Module):
         return out
 
 
+def _encoder_weight_tensors(model: "MixingStyleEncoder", to):
+    """The fields of `mst_encoder_weights` from the module's current parameters and buffers: contiguous fp32 tensors in state_dict
+    layout, the sub-band tensors stacked over the bands.  `to` places each of them: `.cpu()` for `mst_encoder_create`, which
+    reads host arrays, the identity for `mst_encoder_update_params`, which reads them where they are."""
+    ae, fe = model.audio_encoder, model.film_encoder
+    f32 = lambda t: to(t.detach().float()).contiguous()
+    cat = lambda name: f32(torch.stack([getattr(getattr(c, name.split(".")[0]), name.split(".")[1]).detach()
+                                        for c in ae.subnet_cnns], 0))
+    return dict(
+        conv1_w=cat("conv1.weight"), conv1_b=cat("conv1.bias"), bn1_w=cat("bn1.weight"), bn1_b=cat("bn1.bias"),
+        bn1_mean=cat("bn1.running_mean"), bn1_var=cat("bn1.running_var"),
+        conv2_w=cat("conv2.weight"), conv2_b=cat("conv2.bias"), bn2_w=cat("bn2.weight"), bn2_b=cat("bn2.bias"),
+        bn2_mean=cat("bn2.running_mean"), bn2_var=cat("bn2.running_var"),
+        mlp0_w=f32(fe.feature_mlp[0].weight), mlp0_b=f32(fe.feature_mlp[0].bias),
+        mlp3_w=f32(fe.feature_mlp[3].weight), mlp3_b=f32(fe.feature_mlp[3].bias),
+        head_w=f32(fe.film_head.weight), head_b=f32(fe.film_head.bias),
+        att0_w=f32(ae.attention_pooling.attention[0].weight), att0_b=f32(ae.attention_pooling.attention[0].bias),
+        att2_w=f32(ae.attention_pooling.attention[2].weight), att2_b=f32(ae.attention_pooling.attention[2].bias),
+        proj_w=f32(ae.attention_pooling.projection[0].weight), proj_b=f32(ae.attention_pooling.projection[0].bias))
+
+
 class HipEncoder:
     """Owns an `mst_encoder` handle built from a module's current parameters (eval-mode forward in HIP)."""
 
     def __init__(self, model: "MixingStyleEncoder", conv1_precision="fp32"):
         ae, fe = model.audio_encoder, model.film_encoder
-        cpu = lambda t: t.detach().float().cpu().contiguous()
-        cat = lambda name: cpu(torch.stack([getattr(getattr(c, name.split(".")[0]), name.split(".")[1])
-                                            for c in ae.subnet_cnns], 0))
-        self._keep = dict(
-            conv1_w=cat("conv1.weight"), conv1_b=cat("conv1.bias"), bn1_w=cat("bn1.weight"), bn1_b=cat("bn1.bias"),
-            bn1_mean=cat("bn1.running_mean"), bn1_var=cat("bn1.running_var"),
-            conv2_w=cat("conv2.weight"), conv2_b=cat("conv2.bias"), bn2_w=cat("bn2.weight"), bn2_b=cat("bn2.bias"),
-            bn2_mean=cat("bn2.running_mean"), bn2_var=cat("bn2.running_var"),
-            mlp0_w=cpu(fe.feature_mlp[0].weight), mlp0_b=cpu(fe.feature_mlp[0].bias),
-            mlp3_w=cpu(fe.feature_mlp[3].weight), mlp3_b=cpu(fe.feature_mlp[3].bias),
-            head_w=cpu(fe.film_head.weight), head_b=cpu(fe.film_head.bias),
-            att0_w=cpu(ae.attention_pooling.attention[0].weight), att0_b=cpu(ae.attention_pooling.attention[0].bias),
-            att2_w=cpu(ae.attention_pooling.attention[2].weight), att2_b=cpu(ae.attention_pooling.attention[2].bias),
-            proj_w=cpu(ae.attention_pooling.projection[0].weight), proj_b=cpu(ae.attention_pooling.projection[0].bias))
-        w = _lib.EncoderWeights(**{k: v.data_ptr() for k, v in self._keep.items()})
+        keep = _encoder_weight_tensors(model, lambda t: t.cpu())   # host arrays: read before mst_encoder_create returns
+        w = _lib.EncoderWeights(**{k: v.data_ptr() for k, v in keep.items()})
         self.cfg = _lib.EncoderConfig(ae.n_mels, ae.split_size, ae.overlap, ae.n_subbands, fe.feature_dim,
                                       ae.attention_pooling.output_dim, fe.feature_mlp[0].out_features,
                                       ae.attention_pooling.attention[0].out_features, float(ae.subnet_cnns[0].bn1.eps))
@@ -341,24 +349,10 @@ class HipEncoder:
         (`mst_encoder_update_params`): what `hip_encoder()` does before a validation pass that follows optimizer steps
         (src/train.py:388-427 after :292-296) -- no parameter crosses to the host, nothing synchronises.  The module must live
         on a GPU and have the shapes this encoder was created with."""
-        ae, fe = model.audio_encoder, model.film_encoder
-        dev = fe.film_head.weight.device
+        dev = model.film_encoder.film_head.weight.device
         if dev.type != "cuda":
             raise _lib.MstError("HipEncoder.update_from needs the module on a GPU")
-        f32 = lambda t: t.detach().float().contiguous()
-        cat = lambda name: f32(torch.stack([getattr(getattr(c, name.split(".")[0]), name.split(".")[1]).detach()
-                                            for c in ae.subnet_cnns], 0))
-        keep = dict(
-            conv1_w=cat("conv1.weight"), conv1_b=cat("conv1.bias"), bn1_w=cat("bn1.weight"), bn1_b=cat("bn1.bias"),
-            bn1_mean=cat("bn1.running_mean"), bn1_var=cat("bn1.running_var"),
-            conv2_w=cat("conv2.weight"), conv2_b=cat("conv2.bias"), bn2_w=cat("bn2.weight"), bn2_b=cat("bn2.bias"),
-            bn2_mean=cat("bn2.running_mean"), bn2_var=cat("bn2.running_var"),
-            mlp0_w=f32(fe.feature_mlp[0].weight), mlp0_b=f32(fe.feature_mlp[0].bias),
-            mlp3_w=f32(fe.feature_mlp[3].weight), mlp3_b=f32(fe.feature_mlp[3].bias),
-            head_w=f32(fe.film_head.weight), head_b=f32(fe.film_head.bias),
-            att0_w=f32(ae.attention_pooling.attention[0].weight), att0_b=f32(ae.attention_pooling.attention[0].bias),
-            att2_w=f32(ae.attention_pooling.attention[2].weight), att2_b=f32(ae.attention_pooling.attention[2].bias),
-            proj_w=f32(ae.attention_pooling.projection[0].weight), proj_b=f32(ae.attention_pooling.projection[0].bias))
+        keep = _encoder_weight_tensors(model, lambda t: t)
         expect = (self.n_sub, 32, 8, 7, 7)
         if tuple(keep["conv1_w"].shape) != expect or keep["proj_w"].shape[0] != self.embed_dim:
             raise _lib.MstError(f"HipEncoder.update_from: parameter shapes {tuple(keep['conv1_w'].shape)} differ from the encoder's {expect}")
@@ -1068,7 +1062,7 @@ class MixingStyleEncoder(nn.Module):
             # weights changed (optimizer steps, load_state_dict): refresh the existing handle's tables on the device
             self._hip.update_from(self)
             self._hip_version = v
-        elif self._hip is None or v != self._hip_version:   # first use / another precision mode / another device: build (host-side tables)
+        elif self._hip is None or v != self._hip_version:   # first use / another precision mode / another device: build (the same tables from host copies)
             self._hip, self._hip_version = HipEncoder(self, self.conv1_precision), v
             self._hip._dev = self.film_encoder.film_head.weight.device
         return self._hip

@@ -286,7 +286,8 @@ def test_eval_encoder_is_refreshed_on_the_device_after_parameter_updates(precisi
     """src/train.py:388-427 (validate_epoch) follows :292-296 (optimizer steps): the eval encoder must see the new parameters.
     `hip_encoder()` keeps its handle and rebuilds every table ON THE DEVICE (`mst_encoder_update_params`: MFMA fragment swizzles,
     eval BatchNorm fold, float16 fragments + pre-scales, transposes) -- no parameter crosses to the host (checked with torch's
-    sync debug mode) -- and the result equals an encoder built from scratch from the same state_dict."""
+    sync debug mode) -- and the result equals, bit for bit in every precision mode, an encoder built from scratch from the same
+    state_dict."""
     cfg = cases.CFG_DEFAULT
     m = _build(cfg, precision)
     d = _stems(2, 44100, seed=9)
@@ -310,15 +311,74 @@ def test_eval_encoder_is_refreshed_on_the_device_after_parameter_updates(precisi
             torch.cuda.set_sync_debug_mode("default")
         assert enc is first, "the handle is kept, its tables are rebuilt"
         e_after = m(d, feats)
-        fresh = _build(cfg, precision)                            # another module, its encoder built from scratch through the host path
+        fresh = _build(cfg, precision)                            # another module, its encoder built from scratch (mst_encoder_create)
         fresh.load_state_dict(m.state_dict())
         e_fresh = fresh(d, feats)
     assert fresh._hip is not first
     assert (e_after - e_before).abs().max() > 1e-4, "the parameters did change"
-    if precision == "fp32":
-        assert torch.equal(e_after, e_fresh)
-    else:   # the L1 norms behind the range scales are summed in another order on the device: at most a last-bit difference
-        assert (e_after - e_fresh).abs().max().item() <= 2e-6 * e_fresh.abs().max().item()
+    assert torch.equal(e_after, e_fresh)   # creation runs the refresh on staged copies: one builder, the same bits
+
+
+def _extreme_state_dict(cfg):
+    """`cases.make_state_dict` with the filters that take `f16_wstats_kernel`'s other branches: an all-zero filter in each
+    convolution (no finite exponent: pre-scale 2^10), one scaled by 1e-30 (max |w| ~ 4e-32 < 2^-86: the exponent clamps at 100)
+    and one by 1e+20 (a negative exponent)."""
+    sd = cases.make_state_dict(cfg, seed=42)
+    sd["audio_encoder.subnet_cnns.0.conv1.weight"][3].zero_()
+    sd["audio_encoder.subnet_cnns.2.conv2.weight"][17].zero_()
+    sd["audio_encoder.subnet_cnns.1.conv1.weight"][5].mul_(1e-30)
+    sd["audio_encoder.subnet_cnns.4.conv2.weight"][40].mul_(1e+20)
+    return sd
+
+
+def test_zero_tiny_and_huge_filters_give_a_fresh_and_a_refreshed_handle_the_same_bits():
+    """The exponent-clamp and zero-filter branches of the float16 weight statistics, which only the device builder has: a handle
+    created from such weights and one created from ordinary weights and then refreshed to them agree bit for bit in "f16x3-all",
+    both finite; in "fp32" the module agrees with the PyTorch-ROCm backend as any other weights do (1e-4 of the largest value)."""
+    cfg = cases.CFG_DEFAULT
+    sd = _extreme_state_dict(cfg)
+    d = _stems(2, 44100, seed=9)
+    feats = torch.randn(2, 64, generator=torch.Generator().manual_seed(1)).cuda()
+    with torch.no_grad():
+        fresh = _build(cfg, "f16x3-all")
+        fresh.load_state_dict(sd, strict=False)
+        e_fresh = fresh(d, feats)
+        m = _build(cfg, "f16x3-all")
+        m(d, feats)                                   # the handle exists, built from the unmodified weights
+        first = m._hip
+        m.load_state_dict(sd, strict=False)
+        e_refreshed = m(d, feats)
+        assert m._hip is first and fresh._hip is not first
+        m.conv1_precision = "fp32"
+        e_fp32 = m(d, feats)
+        m.encoder_backend = "torch"
+        e_torch = m(d, feats)
+    assert torch.isfinite(e_fresh).all() and torch.isfinite(e_refreshed).all()
+    assert torch.equal(e_fresh, e_refreshed)
+    assert (e_fp32 - e_torch).abs().max().item() <= 1e-4 * e_torch.abs().max().item()
+
+
+def test_refresh_in_a_float16_training_mode_builds_the_eval_tables_once_and_right():
+    """With `set_train_precision("f16")` the trunk refresh inside `mst_encoder_update_params` builds the float16 forward fragments,
+    their pre-scales and the L1 norms, and the full refresh does not build them again: the eval output in mode "f16" after
+    `update_from` equals, bit for bit, that of a fresh module loaded from the same state_dict."""
+    cfg = cases.CFG_DEFAULT
+    d = _stems(2, 44100, seed=9)
+    feats = torch.randn(2, 64, generator=torch.Generator().manual_seed(1)).cuda()
+    with torch.no_grad():
+        m = _build(cfg, "f16")
+        enc = m.hip_encoder()
+        enc.set_train_precision("f16")
+        g = torch.Generator(device="cuda").manual_seed(5)
+        for p in m.parameters():
+            p.add_(torch.randn(p.shape, generator=g, device="cuda") * (0.02 * p.abs().mean()))
+        e_after = m(d, feats)                         # hip_encoder() sees the new parameter versions: update_from
+        assert m._hip is enc and enc.train_mode == 1
+        fresh = _build(cfg, "f16")
+        fresh.load_state_dict(m.state_dict())
+        e_fresh = fresh(d, feats)
+    assert fresh._hip is not enc
+    assert torch.equal(e_after, e_fresh)
 
 
 def test_eval_encoder_sees_running_statistics_updated_without_an_optimizer_step():
