@@ -1,7 +1,9 @@
 """Minimal training loop of the style-transfer stage on the MI355X path: the TCN mixer trains on the HIP kernels
-(`tcn.backend = "hip-train"`: train-mode forward and full backward in libmst.so), the FiLM generator on PyTorch
-(`gen.backend = "torch"`: three small GEMMs, its gradient arrives through the FiLM tensors), the loss is the HIP
-MultiResolutionSTFTLoss.
+(`tcn.backend = "hip-train"`: train-mode forward and full backward in libmst.so), the loss is the HIP
+MultiResolutionSTFTLoss, and the FiLM generator, whose gradient arrives through the FiLM tensors, runs on PyTorch
+(`--film-generator torch`, the default: `gen.backend = "torch"`, three small library GEMMs) or on the HIP kernels as well
+(`--film-generator hip`: `gen.backend = "hip"` with `gen.train_backend = "hip"`, train-mode forward and full backward in
+libmst.so; the step then has no PyTorch module and no library GEMM in it).
 
     python examples/train_tcn_mixer.py --steps 100 --seconds 10 --batch-size 8
 
@@ -25,7 +27,8 @@ PyTorch-ROCm autograd (`--style-encoder torch`, the default: `encoder_backend="t
 (`--style-encoder hip`: `encoder_backend="hip"` with `input_grad_backend="hip"`, the frozen encoder's input gradient on
 hand-written kernels).  The mixing features of `out` condition the encoder as constants, as in the reference ("no grad
 for feature extractor").
-With W = 0 the same seed prints the same losses: every kernel of the step has a fixed summation order."""
+With W = 0 the same seed prints the same losses: every kernel of the step has a fixed summation order (with
+`--film-generator torch` that leans on the GEMM library repeating itself; with `hip` the order is the project's own)."""
 import argparse
 import os
 import sys
@@ -67,6 +70,8 @@ def main(argv=None):
                     help="MixingStyleEncoder checkpoint (a state_dict, or a dict holding 'model_state_dict'); default: random weights")
     ap.add_argument("--style-encoder", choices=("torch", "hip"), default="torch",
                     help="conv trunk of the style term's encoder: PyTorch-ROCm autograd, or the hand-written HIP input gradient")
+    ap.add_argument("--film-generator", choices=("torch", "hip"), default="torch",
+                    help="the FiLM generator's training step: PyTorch-ROCm modules, or the hand-written HIP forward and backward")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("train_tcn_mixer.py needs a GPU (backend='hip-train' has no CPU fallback)")
@@ -75,6 +80,8 @@ def main(argv=None):
     tcn = TCNMixer(hidden_channels=a.hidden, num_blocks=a.blocks, kernel_size=a.kernel_size, use_film=True).to(dev).train()
     gen = TCNFiLMGenerator(embed_dim=2 * a.embed_dim, num_blocks=a.blocks, hidden_channels=a.hidden).to(dev).train()
     tcn.backend, gen.backend = "hip-train", "torch"
+    if a.film_generator == "hip":
+        gen.backend, gen.train_backend = "hip", "hip"
     mrstft = MultiResolutionSTFTLoss()
     opt = torch.optim.AdamW(list(tcn.parameters()) + list(gen.parameters()), lr=a.lr)
 

@@ -656,6 +656,40 @@ int mst_tcn_train_masks(const mst_tcn* tcn, const void* save, size_t save_bytes,
 int mst_tcn_train_conv_grads(const mst_tcn* tcn, int block, int layer, const float* du, const float* in, int B, long long T,
                              float* din, float* dw, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Stage C, training: the FiLM generator (TCNFiLMGenerator src/tcn_mixer.py:148-216; the module the trainer optimises
+ * next to the mixer, src/train_style_transfer.py:255-317), train-mode forward and full backward of
+ *     z1 = W0 x + b0;   h1 = Dropout_p1(LeakyReLU_s(z1))
+ *     z2 = W3 h1 + b3;  h2 = Dropout_p2(LeakyReLU_s(z2))
+ *     film = W6 h2 + b6
+ * emb: dev [B][embed_dim]; film, dfilm: dev [B][out_dim], out_dim = num_blocks * 4 * hidden_channels, i.e. the
+ * [B][num_blocks][4][H] tensor mst_tcn_forward_train reads and mst_tcn_backward writes.  Weights and gradients are DEVICE
+ * tensors in state_dict layout (mst_tcn_film_weights), the module's live parameters by pointer: no handle, nothing swizzled
+ * or cached.  fp32 on v_mfma_f32_16x16x4_f32; every forward product is split-K with the slices added in slice order (the
+ * gamma rounding finding of mst_tcn_film_forward); no float atomics, fixed summation orders: the same seeds give the same
+ * bits, and a row's film does not depend on B.
+ * Dropout: element m * mlp_hidden + n of h1 / h2 is kept iff mst_dropout_mask keeps it under seed1 / seed2; survivors are
+ * scaled by 1 / (1 - p); p == 0 switches a Dropout off.  Masks are never stored: the backward re-derives each decision from
+ * (seed, index) -- behind a LeakyReLU a saved 0 may be a kept unit whose pre-activation was exactly 0 -- and takes slope 1
+ * where the saved activation is > 0, `slope` elsewhere (PyTorch's branch for x <= 0); a dropped unit gets 0.
+ * Limits (refused by name): 1 <= embed_dim <= 4096 (no % 4 rule here), 1 <= mlp_hidden <= 2048, 1 <= out_dim <= 8192,
+ * 1 <= B <= 65535, 0 <= p < 1, 0 <= slope <= 1.  The *_bytes functions return 0 for refused dims; a smaller buffer is
+ * MST_ENOMEM.  No allocation, no host synchronisation, everything on `stream`.
+ * mst_tcn_film_backward: the six parameter gradients are overwritten (not accumulated); demb [B][embed_dim] is written
+ * unless NULL (its GEMM is then skipped).  emb, save and the seeds are what the forward was given and wrote.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct mst_tcn_film_train_dims { int32_t embed_dim, mlp_hidden, out_dim; } mst_tcn_film_train_dims;
+typedef struct mst_tcn_film_grads { float *mlp0_w, *mlp0_b, *mlp3_w, *mlp3_b, *mlp6_w, *mlp6_b; } mst_tcn_film_grads;
+size_t mst_tcn_film_train_save_bytes(const mst_tcn_film_train_dims* dims, int B);
+size_t mst_tcn_film_train_backward_workspace_bytes(const mst_tcn_film_train_dims* dims, int B);
+int mst_tcn_film_forward_train(const mst_tcn_film_train_dims* dims, const mst_tcn_film_weights* w, const float* emb, int B,
+                               float slope, float drop_p1, uint64_t seed1, float drop_p2, uint64_t seed2, float* film,
+                               void* save, size_t save_bytes, void* stream);
+int mst_tcn_film_backward(const mst_tcn_film_train_dims* dims, const mst_tcn_film_weights* w, const float* emb, int B,
+                          float slope, float drop_p1, uint64_t seed1, float drop_p2, uint64_t seed2, const float* dfilm,
+                          const void* save, const mst_tcn_film_grads* grads, float* demb, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

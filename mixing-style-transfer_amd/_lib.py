@@ -116,6 +116,14 @@ class TcnFilmWeights(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("mlp0_w", "mlp0_b", "mlp3_w", "mlp3_b", "mlp6_w", "mlp6_b")]
 
 
+class TcnFilmTrainDims(C.Structure):
+    _fields_ = [("embed_dim", C.c_int32), ("mlp_hidden", C.c_int32), ("out_dim", C.c_int32)]
+
+
+class TcnFilmGrads(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("mlp0_w", "mlp0_b", "mlp3_w", "mlp3_b", "mlp6_w", "mlp6_b")]
+
+
 SYMBOLS = {
     "mst_version": (C.c_int, []),
     "mst_last_error": (C.c_char_p, []),
@@ -241,6 +249,14 @@ SYMBOLS = {
     "mst_tcn_film_destroy": (None, [C.c_void_p]),
     "mst_tcn_film_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "mst_tcn_film_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mst_tcn_film_train_save_bytes": (C.c_size_t, [C.POINTER(TcnFilmTrainDims), C.c_int]),
+    "mst_tcn_film_train_backward_workspace_bytes": (C.c_size_t, [C.POINTER(TcnFilmTrainDims), C.c_int]),
+    "mst_tcn_film_forward_train": (C.c_int, [C.POINTER(TcnFilmTrainDims), C.POINTER(TcnFilmWeights), C.c_void_p, C.c_int, C.c_float,
+                                             C.c_float, C.c_uint64, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t,
+                                             C.c_void_p]),
+    "mst_tcn_film_backward": (C.c_int, [C.POINTER(TcnFilmTrainDims), C.POINTER(TcnFilmWeights), C.c_void_p, C.c_int, C.c_float,
+                                        C.c_float, C.c_uint64, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p,
+                                        C.POINTER(TcnFilmGrads), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 _lib = None

@@ -4,7 +4,8 @@
 //       emb = Dropout(ReLU(Wp pooled + bp))
 //   * the FiLM MLP, reference src/model.py:385-464 --
 //       h1 = Dropout(ReLU(W1 f + b1));  h2 = ReLU(W3 h1 + b3);  film = Wh h2 + bh
-//   * (at the end of the file) the song-identity discriminator and the cosine-distance loss of the adversarial branch
+//   * (at the end of the file) the song-identity discriminator and the cosine-distance loss of the adversarial branch, and the
+//     FiLM generator of the TCN mixer (reference src/tcn_mixer.py:148-216) in training
 // with the gradients autograd derives from them.  fp32 throughout (products on v_mfma_f32_16x16x4_f32 where a GEMM is large
 // enough to matter, fp32 FMA chains elsewhere); every reduction has a fixed order (no atomics): bit-deterministic.
 // Dropout masks are never stored: a keep decision is a pure function of (seed, element index) (Philox-2x32-10, common.h) and
@@ -765,6 +766,134 @@ int mst_cosdist_backward(const float* pred, const float* target, int K, int D, c
   MST_REQUIRE(K >= 1 && D >= 1 && D <= kDiscMaxDim, "mst_cosdist_backward: K=%d rows, D=%d (K >= 1, 1 <= D <= %d)", K, D, kDiscMaxDim);
   hipLaunchKernelGGL(cosdist_bwd_kernel, dim3((K + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pred, target, K, D, save,
                      dloss, dpred);
+  MST_HIP_CHECK(hipGetLastError());
+  return MST_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// TCNFiLMGenerator in training (reference src/tcn_mixer.py:148-216, optimised by src/train_style_transfer.py:255-317) --
+//     h1 = Dropout_p1(LeakyReLU_s(W0 x + b0));  h2 = Dropout_p2(LeakyReLU_s(W3 h1 + b3));  film = W6 h2 + b6
+// The discriminator's structure on the same GEMM kernel, every product split-K (gamma multiplies every activation of the mixer:
+// no single chain over embed_dim or mlp_hidden), with two differences.  The output has up to 8192 columns.  And
+// behind a LeakyReLU a saved zero does not say "dropped": it is a dropped unit (gradient 0) or a kept unit whose pre-activation
+// was exactly 0 (gradient slope * scale * dh), so the backward re-derives every keep decision from (seed, element index) and
+// reads the saved activation only for its sign (h > 0 -> 1, else the slope: PyTorch's branch for x <= 0).
+// ------------------------------------------------------------------------------------------
+namespace {
+constexpr int kSplitGen = kSplitFilm;
+constexpr int kGenMaxEmbed = 4096, kGenMaxHidden = 2048, kGenMaxOut = 8192, kGenMaxRows = 65535;
+struct FinLeaky {   // out[m][n] = Dropout(LeakyReLU(sum + bias[n])), element index m * N + n
+  float* out; const float* bias; int N; float slope; Drop d;
+  __device__ void operator()(long long i, float v) const {
+    float x = v + bias[i % N];
+    x = x > 0.f ? x : x * slope;   // (keeps NaN)
+    out[i] = drop_apply(d, (size_t)i, x);
+  }
+};
+struct FinLeakyMask {   // d pre-activation = keep(seed, i) ? sum * scale * (h > 0 ? 1 : slope) : 0
+  float* out; const float* h; float slope; Drop d;
+  __device__ void operator()(long long i, float v) const {
+    if (d.thresh != 0 && !mst::dropout_keep(d.seed, (size_t)i, d.thresh)) { out[i] = 0.f; return; }
+    const float g = v * d.scale;
+    out[i] = h[i] > 0.f ? g : g * slope;
+  }
+};
+struct GenSave {   // offsets (floats): the two dropped activations, then the forward's split-K partial sums
+  size_t h1, h2, part, total;
+};
+GenSave gen_save(int B, int H, int O) {
+  GenSave s{};
+  s.h1 = 0, s.h2 = (size_t)B * H, s.part = 2 * (size_t)B * H;
+  s.total = s.part + (size_t)kSplitGen * B * std::max(H, O);
+  return s;
+}
+struct GenWork {   // backward scratch: dh2, dh1, split-K partial sums
+  size_t dh2, dh1, part, total;
+};
+GenWork gen_work(int B, int I, int H) {
+  GenWork s{};
+  s.dh2 = 0, s.dh1 = (size_t)B * H, s.part = 2 * (size_t)B * H;
+  s.total = s.part + (size_t)kSplitGen * B * std::max(H, I);
+  return s;
+}
+bool gen_dims_ok(const mst_tcn_film_train_dims* d) {
+  return d->embed_dim >= 1 && d->embed_dim <= kGenMaxEmbed && d->mlp_hidden >= 1 && d->mlp_hidden <= kGenMaxHidden && d->out_dim >= 1 &&
+         d->out_dim <= kGenMaxOut;
+}
+// the limits both entry points share, refused under the caller's name `fn`
+int gen_check(const char* fn, const mst_tcn_film_train_dims* dm, int B, float p1, float p2, float slope) {
+  MST_REQUIRE(gen_dims_ok(dm), "%s: dims out of range (embed_dim=%d in 1..%d, mlp_hidden=%d in 1..%d, out_dim=%d in 1..%d)", fn,
+              dm->embed_dim, kGenMaxEmbed, dm->mlp_hidden, kGenMaxHidden, dm->out_dim, kGenMaxOut);
+  MST_REQUIRE(B >= 1 && B <= kGenMaxRows, "%s: B=%d rows, must be in 1..%d", fn, B, kGenMaxRows);
+  MST_REQUIRE(p1 >= 0.f && p1 < 1.f && p2 >= 0.f && p2 < 1.f, "%s: dropout p must be in [0, 1)", fn);
+  MST_REQUIRE(slope >= 0.f && slope <= 1.f, "%s: LeakyReLU slope must be in [0, 1]", fn);
+  return MST_OK;
+}
+}  // namespace
+
+extern "C" {
+
+size_t mst_tcn_film_train_save_bytes(const mst_tcn_film_train_dims* d, int B) {
+  if (!d || B <= 0 || B > kGenMaxRows || !gen_dims_ok(d)) return 0;
+  return gen_save(B, d->mlp_hidden, d->out_dim).total * sizeof(float);
+}
+size_t mst_tcn_film_train_backward_workspace_bytes(const mst_tcn_film_train_dims* d, int B) {
+  if (!d || B <= 0 || B > kGenMaxRows || !gen_dims_ok(d)) return 0;
+  return gen_work(B, d->embed_dim, d->mlp_hidden).total * sizeof(float);
+}
+
+int mst_tcn_film_forward_train(const mst_tcn_film_train_dims* dm, const mst_tcn_film_weights* w, const float* emb, int B, float slope,
+                               float drop_p1, uint64_t seed1, float drop_p2, uint64_t seed2, float* film, void* save, size_t save_bytes,
+                               void* stream) {
+  MST_REQUIRE(dm && w && emb && film && save, "mst_tcn_film_forward_train: NULL argument");
+  MST_REQUIRE(w->mlp0_w && w->mlp0_b && w->mlp3_w && w->mlp3_b && w->mlp6_w && w->mlp6_b, "mst_tcn_film_forward_train: NULL weight");
+  if (const int rc = gen_check("mst_tcn_film_forward_train", dm, B, drop_p1, drop_p2, slope)) return rc;
+  const int I = dm->embed_dim, H = dm->mlp_hidden, O = dm->out_dim;
+  const GenSave S = gen_save(B, H, O);
+  if (save_bytes < S.total * sizeof(float))
+    return mst::fail(MST_ENOMEM, "mst_tcn_film_forward_train: save buffer %zu B < %zu B", save_bytes, S.total * sizeof(float));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  float* sv = static_cast<float*>(save);
+  const Drop d1 = make_drop(drop_p1, seed1), d2 = make_drop(drop_p2, seed2);
+  gemm_split<false, false>(B, H, I, kSplitGen, RowMajA{emb, I}, RowMajT{w->mlp0_w, I}, sv + S.part, FinLeaky{sv + S.h1, w->mlp0_b, H, slope, d1}, st);
+  gemm_split<false, false>(B, H, H, kSplitGen, RowMajA{sv + S.h1, H}, RowMajT{w->mlp3_w, H}, sv + S.part, FinLeaky{sv + S.h2, w->mlp3_b, H, slope, d2}, st);
+  gemm_split<false, false>(B, O, H, kSplitGen, RowMajA{sv + S.h2, H}, RowMajT{w->mlp6_w, H}, sv + S.part, FinLin{film, w->mlp6_b, O, 0, make_drop(0.f, 0)}, st);
+  MST_HIP_CHECK(hipGetLastError());
+  return MST_OK;
+}
+
+int mst_tcn_film_backward(const mst_tcn_film_train_dims* dm, const mst_tcn_film_weights* w, const float* emb, int B, float slope,
+                          float drop_p1, uint64_t seed1, float drop_p2, uint64_t seed2, const float* dfilm, const void* save,
+                          const mst_tcn_film_grads* g, float* demb, void* workspace, size_t workspace_bytes, void* stream) {
+  MST_REQUIRE(dm && w && emb && dfilm && save && g && workspace, "mst_tcn_film_backward: NULL argument");
+  MST_REQUIRE(w->mlp0_w && w->mlp0_b && w->mlp3_w && w->mlp3_b && w->mlp6_w && w->mlp6_b, "mst_tcn_film_backward: NULL weight");
+  MST_REQUIRE(g->mlp0_w && g->mlp0_b && g->mlp3_w && g->mlp3_b && g->mlp6_w && g->mlp6_b, "mst_tcn_film_backward: NULL gradient pointer");
+  if (const int rc = gen_check("mst_tcn_film_backward", dm, B, drop_p1, drop_p2, slope)) return rc;
+  const int I = dm->embed_dim, H = dm->mlp_hidden, O = dm->out_dim;
+  const GenSave S = gen_save(B, H, O);
+  const GenWork Wk = gen_work(B, I, H);
+  if (workspace_bytes < Wk.total * sizeof(float))
+    return mst::fail(MST_ENOMEM, "mst_tcn_film_backward: workspace %zu B < %zu B", workspace_bytes, Wk.total * sizeof(float));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const float* sv = static_cast<const float*>(save);
+  const float *h1 = sv + S.h1, *h2 = sv + S.h2;
+  float* ws = static_cast<float*>(workspace);
+  float *dh2 = ws + Wk.dh2, *dh1 = ws + Wk.dh1, *part = ws + Wk.part;
+  const Drop d1 = make_drop(drop_p1, seed1), d2 = make_drop(drop_p2, seed2);
+  const dim3 blk(256);
+  auto wgrad = [&](const float* dy, int N, const float* in, int K, float* dw, float* db) {   // db = colsum(dy), dw = dy^T in
+    hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64), blk, 0, st, dy, db, B, N);
+    hipLaunchKernelGGL((gemm_kernel<true, true, ColMajA, RowMajB, EpiStore>), dim3((K + 63) / 64, (N + 63) / 64, 1), blk, 0, st, N, K, B, 1,
+                       round_up(B, kKC), ColMajA{dy, N}, RowMajB{in, K}, EpiStore{dw, K});
+  };
+  wgrad(dfilm, O, h2, H, g->mlp6_w, g->mlp6_b);
+  gemm_split<false, true>(B, H, O, kSplitGen, RowMajA{dfilm, O}, RowMajB{w->mlp6_w, H}, part, FinLeakyMask{dh2, h2, slope, d2}, st);
+  wgrad(dh2, H, h1, H, g->mlp3_w, g->mlp3_b);
+  gemm_split<false, true>(B, H, H, kSplitGen, RowMajA{dh2, H}, RowMajB{w->mlp3_w, H}, part, FinLeakyMask{dh1, h1, slope, d1}, st);
+  wgrad(dh1, H, emb, I, g->mlp0_w, g->mlp0_b);
+  if (demb) gemm_split<false, true>(B, I, H, kSplitGen, RowMajA{dh1, H}, RowMajB{w->mlp0_w, I}, part, FinStore{demb}, st);
   MST_HIP_CHECK(hipGetLastError());
   return MST_OK;
 }

@@ -13,6 +13,10 @@ Same class names, constructor arguments, defaults and `state_dict` keys as the r
     backward returns the gradients of x, of the FiLM tensors and of every parameter.  In `eval()` without gradients it
     is the inference path of "hip".  The device weights follow in-place parameter updates (an optimiser step) through a
     device kernel, without a host copy.  CUDA fp32 only; `eval()` with gradients raises and names `backend = "torch"`.
+  * `train_backend = "hip"` (TCNFiLMGenerator only, next to `backend = "hip"`; default "none"): a call in `train()` mode
+    or one that needs a gradient runs `mst_tcn_film_forward_train` / `mst_tcn_film_backward` (csrc/head.hip) as an autograd
+    function on the module's live parameters: Dropout from seeds of torch's CPU generator, all six parameter gradients and,
+    when the embedding requires one, its gradient.  `eval()` without gradients stays on the inference handle.
 """
 import ctypes as C
 import math
@@ -22,6 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from .model import _seed64
 
 STEM_ORDER = ("vocals", "bass", "drums", "other")
 _BACKENDS = ("hip", "torch")
@@ -171,7 +176,39 @@ class TCNFiLMGenerator(nn.Module):
                 nn.init.normal_(layer.weight, mean=0.0, std=0.01)
                 nn.init.zeros_(layer.bias)
         self.backend = "hip"
+        # training with backend == "hip": "none" (default) = there is none (train() mode or a needed gradient raises and names
+        # backend="torch"); "hip" = train-mode forward and full backward in libmst.so (_FiLMTrainFn) for a call in train() mode or
+        # one that needs a gradient -- eval() without gradients stays on the inference handle
+        self.train_backend = "none"
         self._hip = None
+
+    def _train_params(self):
+        """The parameters in the order of mst_tcn_film_weights / mst_tcn_film_grads."""
+        return [self.mlp[0].weight, self.mlp[0].bias, self.mlp[3].weight, self.mlp[3].bias, self.mlp[6].weight, self.mlp[6].bias]
+
+    def _film_tensor_train(self, emb):
+        what = "TCNFiLMGenerator.forward (train_backend='hip')"
+        slopes = {float(self.mlp[1].negative_slope), float(self.mlp[4].negative_slope)}
+        if len(slopes) != 1:
+            raise ValueError(f"{what}: one LeakyReLU slope for both layers is built, got {sorted(slopes)}; backend='torch' runs "
+                             f"the plain module tree")
+        params = self._train_params()
+        msg = _tensor_refusal(what, emb, *params)
+        if msg is None and any(p.device != emb.device for p in params):
+            msg = f"{what}: the embedding is on {emb.device} and a parameter on {next(p.device for p in params if p.device != emb.device)}; the kernels need one device"
+        if msg is None and not all(p.is_contiguous() for p in params):
+            msg = f"{what}: the kernels read the live parameters by pointer and need them contiguous"
+        if msg:
+            _raise_refusal(msg)
+        if emb.dim() != 2 or emb.shape[1] != self.mlp[0].in_features:
+            raise ValueError(f"expected (B, {self.mlp[0].in_features}) embeddings, got {tuple(emb.shape)}")
+        B = emb.shape[0]
+        if self.mlp[6].out_features != self.num_blocks * 4 * self.hidden_channels:
+            raise ValueError(f"{what}: mlp[6] has {self.mlp[6].out_features} outputs, expected num_blocks * 4 * hidden_channels")
+        if B == 0:
+            return torch.empty(0, self.num_blocks, 4, self.hidden_channels, device=emb.device, dtype=torch.float32)
+        p1, p2 = (float(self.mlp[i].p) if self.training else 0.0 for i in (2, 5))
+        return _FiLMTrainFn.apply(emb, (self.num_blocks, 4, self.hidden_channels), slopes.pop(), p1, p2, *params)
 
     def _handle(self, device):
         key = _state_key(self)
@@ -189,9 +226,14 @@ class TCNFiLMGenerator(nn.Module):
         """(B, num_blocks, 4, hidden_channels): gamma1, beta1, gamma2, beta2 per block."""
         if self.backend not in _BACKENDS:
             raise ValueError("backend must be 'hip' (default) or 'torch'")
+        if self.train_backend not in ("none", "hip"):
+            raise ValueError("train_backend must be 'none' (default) or 'hip'")
         B = concat_embeddings.shape[0]
         if self.backend == "torch":
             return self.mlp(concat_embeddings).view(B, self.num_blocks, 4, self.hidden_channels)
+        if self.train_backend == "hip" and (self.training or (torch.is_grad_enabled() and (
+                concat_embeddings.requires_grad or any(p.requires_grad for p in self.parameters())))):
+            return self._film_tensor_train(concat_embeddings)
         msg = _hip_refusal(self, "TCNFiLMGenerator.forward", concat_embeddings)
         if msg:
             _raise_refusal(msg)
@@ -217,6 +259,50 @@ class TCNFiLMGenerator(nn.Module):
                  "beta2": params[:, i, 3, :]} for i in range(self.num_blocks)]
 
 
+class _FiLMTrainFn(torch.autograd.Function):
+    """TCNFiLMGenerator's MLP for training, forward and backward in libmst.so (`mst_tcn_film_forward_train` /
+    `mst_tcn_film_backward`, csrc/head.hip): fp32, split-K in a fixed order, Dropout masks re-derived from (seed, element).
+    The kernels read the module's live parameters by pointer; the save buffer belongs to the call."""
+
+    @staticmethod
+    def forward(ctx, emb, shape, slope, p1, p2, *params):
+        x = emb.contiguous()
+        B, dev = x.shape[0], x.device
+        dims = _lib.TcnFilmTrainDims(params[0].shape[1], params[0].shape[0], params[4].shape[0])
+        seeds = (_seed64() if p1 > 0.0 else 0, _seed64() if p2 > 0.0 else 0)
+        L = _lib.lib()
+        nsave = L.mst_tcn_film_train_save_bytes(C.byref(dims), B)
+        save = torch.empty(nsave, dtype=torch.uint8, device=dev)
+        film = torch.empty(B, *shape, device=dev, dtype=torch.float32)
+        wp = _lib.TcnFilmWeights(*[p.data_ptr() for p in params])
+        with torch.cuda.device(dev):
+            _lib.check(L.mst_tcn_film_forward_train(C.byref(dims), C.byref(wp), _lib.dptr(x), B, slope, p1, seeds[0], p2, seeds[1],
+                                                    _lib.dptr(film), _lib.dptr(save), nsave, _lib.stream_ptr(dev)),
+                       "mst_tcn_film_forward_train")
+        ctx.cfg = (dims, slope, p1, p2, seeds)
+        ctx.save_for_backward(x, save, *params)   # (autograd's version check covers the parameters the backward reads again)
+        return film
+
+    @staticmethod
+    def backward(ctx, dfilm):
+        x, save, *params = ctx.saved_tensors
+        dims, slope, p1, p2, seeds = ctx.cfg
+        B, dev = x.shape[0], x.device
+        L = _lib.lib()
+        grads = [torch.empty_like(p) for p in params]
+        demb = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        nws = L.mst_tcn_film_train_backward_workspace_bytes(C.byref(dims), B)
+        work = torch.empty(nws, dtype=torch.uint8, device=dev)
+        df = dfilm.contiguous()
+        wp = _lib.TcnFilmWeights(*[p.data_ptr() for p in params])
+        gp = _lib.TcnFilmGrads(*[g.data_ptr() for g in grads])
+        with torch.cuda.device(dev):
+            _lib.check(L.mst_tcn_film_backward(C.byref(dims), C.byref(wp), _lib.dptr(x), B, slope, p1, seeds[0], p2, seeds[1], _lib.dptr(df),
+                                               _lib.dptr(save), C.byref(gp), _lib.dptr(demb), _lib.dptr(work), nws, _lib.stream_ptr(dev)),
+                       "mst_tcn_film_backward")
+        return (demb, None, None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[5:]))
+
+
 _FILM_KEYS = ("gamma1", "beta1", "gamma2", "beta2")
 
 
@@ -229,6 +315,25 @@ def _packed_film(film_params, B, nb, H):
            for i in range(nb) for q, k in enumerate(_FILM_KEYS) for t in (film_params[i][k],)):
         return first.as_strided((B, nb, 4, H), (nb * 4 * H, 4 * H, H, 1))
     return torch.stack([torch.stack([film_params[i][k] for k in _FILM_KEYS], 1) for i in range(nb)], 1).contiguous()
+
+
+def _film_base(film_params, B, nb, H):
+    """The (B, nb, 4, H) tensor the dicts are the plain slices of, as AUTOGRAD knows it (the views' common `_base`, e.g. the
+    generator's output): its gradient is the slices' gradients side by side, so it can stand for them without a copy.  None
+    when the dicts are anything else.  With the base as the function's input the slices are no longer nodes of the graph, so
+    the stack is kept wherever that could be seen: a slice that is not connected to the base as the base's `requires_grad`
+    says it should be (taken under `torch.no_grad()`, it has no `grad_fn` and the stack sends no gradient into the base), a
+    slice with `retain_grad()` or a tensor hook on it."""
+    base = getattr(film_params[0]["gamma1"], "_base", None)   # (a private attribute: without it, the stack)
+    if base is None or base.numel() != B * nb * 4 * H or not base.is_contiguous() or base.dtype != torch.float32:
+        return None
+    es, p0 = base.element_size(), base.data_ptr()
+    if all(t._base is base and t.data_ptr() == p0 + (i * 4 + q) * H * es and tuple(t.shape) == (B, H) and t.stride() == (nb * 4 * H, 1)
+           and t.requires_grad == base.requires_grad and (t.grad_fn is not None) == base.requires_grad
+           and not t.retains_grad and not t._backward_hooks
+           for i in range(nb) for q, k in enumerate(_FILM_KEYS) for t in (film_params[i][k],)):
+        return base.view(B, nb, 4, H)
+    return None
 
 
 class TCNMixer(nn.Module):
@@ -438,7 +543,9 @@ class TCNMixer(nn.Module):
         if x.numel() == 0:
             raise ValueError(f"{what}: empty input {tuple(x.shape)}")
         film = None
-        if self.use_film:   # stacked with ops autograd follows (not the as_strided view of _packed_film)
+        if self.use_film:
+            film = _film_base(film_params, B, nb, H)
+        if self.use_film and film is None:   # stacked with ops autograd follows (not the as_strided view of _packed_film)
             film = torch.stack([torch.stack([film_params[i][k] for k in _FILM_KEYS], 1) for i in range(nb)], 1)
             if tuple(film.shape) != (B, nb, 4, H):
                 raise ValueError(f"expected FiLM tensors of shape ({B}, {H}), got a stack of {tuple(film.shape)}")
