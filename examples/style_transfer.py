@@ -8,6 +8,7 @@ inference/inference_e2e_style_transfer.py does once the stems are separated:
 
     python examples/style_transfer.py                       # two seeded synthetic clips, seeded weights
     python examples/style_transfer.py --tcn_checkpoint ckpt.pt --encoder_checkpoint enc.pt --seconds 10
+    python examples/style_transfer.py --tcn-precision f16x3 # the mixer's convolutions in split precision on the f16 MFMA
     python examples/style_transfer.py --cycle               # + the cycle-consistency distance of the trainer (no gradient step)
 
 --tcn_checkpoint is the reference's format (train_style_transfer.py): a dict with `tcn_state_dict`,
@@ -47,6 +48,8 @@ def main(argv=None):
     ap.add_argument("--tcn_checkpoint", default=None)
     ap.add_argument("--encoder_checkpoint", default=None, help="state_dict of MixingStyleEncoder (reference format)")
     ap.add_argument("--backend", choices=["hip", "torch"], default="hip")
+    ap.add_argument("--tcn-precision", choices=["fp32", "f16x3"], default="fp32",
+                    help="TCNMixer.precision of the hip backend: f16x3 = split-precision inference on the f16 MFMA (pays on wide mixers)")
     ap.add_argument("--cycle", action="store_true",
                     help="also send the processed stems back (style of the input) and print the MR-STFT distance to the input stems")
     a = ap.parse_args(argv)
@@ -72,12 +75,13 @@ def main(argv=None):
         gen.load_state_dict(ck["film_generator_state_dict"])
     tcn, gen = tcn.to(device), gen.to(device)
     tcn.backend = gen.backend = a.backend
+    tcn.precision = a.tcn_precision
 
     stems_in = {s: x[0, 2 * i:2 * i + 2] for i, s in enumerate(STEMS)}
     out = apply_style_transfer(tcn, gen, stems_in, e_tgt, e_in, device)
     y = torch.cat([out["processed_stems"][s] for s in STEMS], 0)
     e_out = embed(encoder, y, device)
-    print(f"TCN: {nb} blocks, {H} channels, receptive field {tcn.receptive_field} samples, backend {a.backend}")
+    print(f"TCN: {nb} blocks, {H} channels, receptive field {tcn.receptive_field} samples, backend {a.backend}, precision {a.tcn_precision}")
     print(f"processed mixture {tuple(out['processed_mixture'].shape)}, max |y - x| = {float((y - x[0]).abs().max()):.4f}")
     print(f"cosine distance to the target: input {distance(e_in, e_tgt):.4f} -> processed {distance(e_out, e_tgt):.4f}")
     if a.cycle:   # train_style_transfer.py:228-239: output -> reconstructed input, MultiResolutionSTFTLoss(reconstructed, input)

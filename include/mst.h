@@ -607,6 +607,18 @@ size_t mst_tcn_workspace_bytes(const mst_tcn* tcn, int B, long long T);
  * block (what mst_tcn_film_forward writes); required iff use_film.  taps may be NULL.                            */
 int mst_tcn_forward(const mst_tcn* tcn, const float* x, const float* film, int B, long long T, float* y,
                     const mst_tcn_taps* taps, void* workspace, size_t workspace_bytes, void* stream);
+/* Opt-in split-precision inference of the dilated convolutions on the f16 matrix pipe (csrc/tcn_f16x3.inc).
+ * MST_TCN_FP32 (default): the exact-fp32 MFMA kernels.  MST_TCN_F16X3: activations and filters as hi + lo f16 (22
+ * significant bits together), three f16 MFMA products per term with fp32 accumulation (only lo * lo is dropped), an exact
+ * power-of-two range scale per (convolution, clip) and per (convolution, output channel) derived on the device; same
+ * parity bar as fp32, bit-reproducible, a clip's result does not depend on its batch.  mst_tcn_set_precision builds the
+ * f16 weight fragments from the handle's weights on `stream` (mst_tcn_update_params rebuilds them while the mode is on)
+ * and returns MST_EINVAL for an unknown mode.  mst_tcn_workspace_bytes and mst_tcn_forward follow the handle's mode (the
+ * workspace grows by two f16 planes and the absmax array; H padded to 32 times T must stay below 2^31).  The training
+ * entry points (mst_tcn_forward_train, mst_tcn_backward, mst_tcn_train_*) IGNORE the mode and compute in fp32.          */
+enum { MST_TCN_FP32 = 0, MST_TCN_F16X3 = 1 };
+int mst_tcn_set_precision(mst_tcn* tcn, int mode, void* stream);
+int mst_tcn_get_precision(const mst_tcn* tcn);
 /* Linear(embed_dim, 512) - LeakyReLU - Linear(512, 512) - LeakyReLU - Linear(512, num_blocks*4*hidden); embed_dim % 4 == 0. */
 int mst_tcn_film_create(mst_tcn_film** out, int embed_dim, int num_blocks, int hidden, const mst_tcn_film_weights* w);
 void mst_tcn_film_destroy(mst_tcn_film* gen);

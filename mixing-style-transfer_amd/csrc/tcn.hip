@@ -319,7 +319,20 @@ struct mst_tcn {
   // training only, allocated by the first mst_tcn_update_params: the transposed, tap-reversed weights of the input
   // gradient in A-fragment order, and [2 nb + 1][2][HP] = (1, conv bias) per convolution, then one entry of zeros
   float *wswT, *rawsc;
+  // f16x3 mode only (tcn_f16x3.inc), allocated by the first mst_tcn_set_precision(MST_TCN_F16X3): hi / lo f16 weight
+  // fragments and the power-of-two exponent of every (convolution, output channel); mode: MST_TCN_FP32 / MST_TCN_F16X3
+  void* wf;
+  int* wexp;
+  int mode;
 };
+
+namespace mst {   // tcn_f16x3.inc
+size_t tcn_f16x3_extra_bytes(const mst_tcn* h, int B, long long T);
+int tcn_f16x3_shape_ok(const mst_tcn* h, long long T, const char* who);
+int tcn_f16x3_build(mst_tcn* h, hipStream_t st);
+int tcn_forward_f16x3(const mst_tcn* h, const float* x, const float* film, int B, long long T, float* y, const mst_tcn_taps* taps,
+                      void* ws, hipStream_t st);
+}  // namespace mst
 
 struct mst_tcn_film {
   int E, nb, H;
@@ -335,6 +348,8 @@ void mst_tcn_destroy(mst_tcn* h) {
   float* p[] = {h->wsw, h->wi, h->bi, h->wo, h->bo, h->cb, h->bw, h->bb, h->bm, h->bv, h->wswT, h->rawsc};
   for (float* q : p)
     if (q) (void)hipFree(q);
+  if (h->wf) (void)hipFree(h->wf);
+  if (h->wexp) (void)hipFree(h->wexp);
   delete h;
 }
 
@@ -415,12 +430,15 @@ static size_t tcn_sc_floats(const mst_tcn* h, int B) { return (size_t)B * h->cfg
 
 size_t mst_tcn_workspace_bytes(const mst_tcn* h, int B, long long T) {
   if (tcn_shape_ok(h, B, T, "mst_tcn_workspace_bytes") != MST_OK) return 0;
-  return 2 * align_up((size_t)B * T * h->HP * sizeof(float), 256) + align_up(tcn_sc_floats(h, B) * sizeof(float), 256);
+  if (h->mode == MST_TCN_F16X3 && tcn_f16x3_shape_ok(h, T, "mst_tcn_workspace_bytes") != MST_OK) return 0;
+  return 2 * align_up((size_t)B * T * h->HP * sizeof(float), 256) + align_up(tcn_sc_floats(h, B) * sizeof(float), 256) +
+         (h->mode == MST_TCN_F16X3 ? tcn_f16x3_extra_bytes(h, B, T) : 0);
 }
 
 int mst_tcn_forward(const mst_tcn* h, const float* x, const float* film, int B, long long T, float* y, const mst_tcn_taps* taps,
                     void* ws, size_t ws_bytes, void* stream) {
   int rc = tcn_shape_ok(h, B, T, "mst_tcn_forward");
+  if (rc == MST_OK && h->mode == MST_TCN_F16X3) rc = tcn_f16x3_shape_ok(h, T, "mst_tcn_forward");
   if (rc != MST_OK) return rc;
   MST_REQUIRE(x && y && ws, "mst_tcn_forward: NULL pointer");
   MST_REQUIRE(!h->cfg.use_film == !film, "mst_tcn_forward: film parameters are %s for this mixer (use_film = %d)",
@@ -434,6 +452,7 @@ int mst_tcn_forward(const mst_tcn* h, const float* x, const float* film, int B, 
                   taps->block[i]);
   }
   hipStream_t st = (hipStream_t)stream;
+  if (h->mode == MST_TCN_F16X3) return tcn_forward_f16x3(h, x, film, B, T, y, taps, ws, st);
   const int H = h->cfg.hidden_channels, HP = h->HP, K = h->cfg.kernel_size, nb = h->cfg.num_blocks;
   const size_t hb = align_up((size_t)B * T * HP * sizeof(float), 256);
   float* hbuf = (float*)ws;
@@ -520,4 +539,5 @@ int mst_tcn_film_forward(const mst_tcn_film* f, const float* emb, int B, float* 
 
 }  // extern "C"
 
+#include "tcn_f16x3.inc"
 #include "tcn_train.inc"

@@ -455,6 +455,10 @@ int mst_tcn_update_params(mst_tcn* h, const mst_tcn_weights* w, void* stream) {
     }
     hipLaunchKernelGGL(tcn_swizzle_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, w->conv_w, h->wsw, h->wswT, (long long)nw,
                        H, HP, K);
+    if (h->mode == MST_TCN_F16X3) {   // the f16 fragments follow wsw: never stale
+      const int rc = tcn_f16x3_build(h, st);
+      if (rc != MST_OK) return rc;
+    }
     hipLaunchKernelGGL(tcn_small_params_kernel, dim3(1), dim3(kMaxHidden), 0, st, w->input_w, w->input_b, w->output_w, w->output_b,
                        w->conv_b, H, HP, 2 * nb, h->wi, h->bi, h->wo, h->bo, h->rawsc);
     const struct { float* d; const float* s; } cp[] = {{h->cb, w->conv_b}, {h->bw, w->bn_w}, {h->bb, w->bn_b}};

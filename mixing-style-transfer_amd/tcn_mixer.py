@@ -6,6 +6,8 @@ Same class names, constructor arguments, defaults and `state_dict` keys as the r
 
   * `backend = "hip"` (default): inference on the kernels of `csrc/tcn.hip` (exact fp32 MFMA).  Needs `eval()`, CUDA
     tensors, fp32 and no gradients; anything else RAISES and names the opt-in (no silent library path, no CPU fallback).
+    `TCNMixer.precision = "f16x3"` (default "fp32") is the opt-in split-precision mode of this path: the dilated
+    convolutions on the f16 MFMA with hi + lo operands (csrc/tcn_f16x3.inc), same parity bar, inference only.
   * `backend = "torch"`: the plain module tree on PyTorch (any device, any dtype, autograd).  It is the opt-in for
     training and the arithmetic the tests pin to the reference.
   * `backend = "hip-train"` (TCNMixer only): training on the kernels of `csrc/tcn_train.inc`.  In `train()` mode the
@@ -31,6 +33,7 @@ from .model import _seed64
 STEM_ORDER = ("vocals", "bass", "drums", "other")
 _BACKENDS = ("hip", "torch")
 _MIXER_BACKENDS = _BACKENDS + ("hip-train",)
+_PRECISIONS = {"fp32": 0, "f16x3": 1}   # MST_TCN_FP32, MST_TCN_F16X3
 
 
 class CausalConv1d(nn.Module):
@@ -357,6 +360,9 @@ class TCNMixer(nn.Module):
         nn.init.zeros_(self.output_conv.bias)
         self.receptive_field = 1 + sum(2 ** i * (kernel_size - 1) for i in range(num_blocks))
         self.backend = "hip"
+        # backend == "hip" only: "fp32" (default) = the exact-fp32 MFMA kernels; "f16x3" = split-precision inference on the
+        # f16 MFMA (mst_tcn_set_precision).  "hip-train" refuses "f16x3"; "torch" does not read it
+        self.precision = "fp32"
         self._hip = None
 
     # ---- torch tree ------------------------------------------------------------------------------------------------
@@ -407,6 +413,9 @@ class TCNMixer(nn.Module):
             return y, taps_out
         L = _lib.lib()
         with torch.cuda.device(dev):
+            if getattr(h, "precision", "fp32") != self.precision:   # on first use and on change; a new handle starts in fp32
+                _lib.check(L.mst_tcn_set_precision(h.ptr, _PRECISIONS[self.precision], _lib.stream_ptr(dev)), "mst_tcn_set_precision")
+                h.precision = self.precision
             per_clip = L.mst_tcn_workspace_bytes(h.ptr, 1, T)
             if per_clip == 0:
                 _lib.check(-1, "mst_tcn_workspace_bytes")
@@ -564,8 +573,13 @@ class TCNMixer(nn.Module):
             raise ValueError("backend must be 'hip' (default), 'torch' or 'hip-train'")
         if self.backend == "torch":
             return self._forward_torch(x, film_params)
+        if self.precision not in _PRECISIONS:
+            raise ValueError(f"precision must be 'fp32' (default) or 'f16x3', got {self.precision!r}")
         fl = [p[k] for p in film_params for k in _FILM_KEYS] if self.use_film else []
         if self.backend == "hip-train":
+            if self.precision != "fp32":
+                _raise_refusal(f"TCNMixer.forward (backend='hip-train'): precision={self.precision!r} is inference only (the "
+                               f"training kernels compute in fp32); set precision='fp32', or backend='hip' for f16x3 inference")
             return self._forward_hip_train(x, film_params, fl)
         msg = _hip_refusal(self, "TCNMixer.forward", x, *fl)
         if msg:
