@@ -25,8 +25,9 @@ through a FROZEN MixingStyleEncoder in eval mode (`--encoder-checkpoint`, else r
 the TCN through the encoder's input waveform: stage A (STFT -> mel -> log) forward and backward in HIP, the conv trunk on
 PyTorch-ROCm autograd (`--style-encoder torch`, the default: `encoder_backend="torch"`) or in HIP as well
 (`--style-encoder hip`: `encoder_backend="hip"` with `input_grad_backend="hip"`, the frozen encoder's input gradient on
-hand-written kernels).  The mixing features of `out` condition the encoder as constants, as in the reference ("no grad
-for feature extractor").
+hand-written kernels).  The mixing features of `out` condition the encoder as constants by default (`--style-features
+const`); `--style-features grad` differentiates them too, as the reference does (it extracts the output's features with
+gradients): `feature_grad_backend="hip"`, stage A's feature gradient fused with the log-mel's.
 With W = 0 the same seed prints the same losses: every kernel of the step has a fixed summation order (with
 `--film-generator torch` that leans on the GEMM library repeating itself; with `hip` the order is the project's own)."""
 import argparse
@@ -70,6 +71,9 @@ def main(argv=None):
                     help="MixingStyleEncoder checkpoint (a state_dict, or a dict holding 'model_state_dict'); default: random weights")
     ap.add_argument("--style-encoder", choices=("torch", "hip"), default="torch",
                     help="conv trunk of the style term's encoder: PyTorch-ROCm autograd, or the hand-written HIP input gradient")
+    ap.add_argument("--style-features", choices=("const", "grad"), default="const",
+                    help="mixing features of the style term: constants (default), or differentiated as the reference does "
+                         "(feature_grad_backend='hip': the second path from the waveform to the embedding)")
     ap.add_argument("--film-generator", choices=("torch", "hip"), default="torch",
                     help="the FiLM generator's training step: PyTorch-ROCm modules, or the hand-written HIP forward and backward")
     a = ap.parse_args(argv)
@@ -98,6 +102,8 @@ def main(argv=None):
         encoder = MixingStyleEncoder(embed_dim=a.embed_dim, feature_dim=64, encoder_backend=a.style_encoder)
         if a.style_encoder == "hip":
             encoder.input_grad_backend = "hip"
+        if a.style_features == "grad":
+            encoder.feature_grad_backend = "hip"
         if a.encoder_checkpoint:
             sd = torch.load(a.encoder_checkpoint, map_location="cpu")
             encoder.load_state_dict(sd.get("model_state_dict", sd))

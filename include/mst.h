@@ -360,8 +360,13 @@ int mst_encoder_train_conv2_dgrad(const mst_encoder* enc, const float* dy2, int 
  * mst_encoder_frozen_backward_apply: backward of max-pool -> ReLU -> affine of conv layer 1 or 2:
  *   dy[band][B][C][rows][cols] = A(clip, band, ch) * dpool at the first arg-max (row-major) of every pooling window whose
  *   maximum is positive, 0 elsewhere.  dpool: layer 1 [B][n_sub][32][H1][W1], layer 2 [B][64*n_sub*freq_dim][W2], given by
- *   its clip / band / channel strides in floats (rows are the pooled width apart).  No FiLM gradient: the mixing
- *   features are constants on this path.
+ *   its clip / band / channel strides in floats (rows are the pooled width apart).  No FiLM gradient here: see
+ *   mst_encoder_frozen_film_grad.
+ * mst_encoder_frozen_film_grad: the gradient to the FiLM tensor of conv layer 1 or 2 from the same dpool (for a caller that
+ *   differentiates the mixing features): with z = gamma u + beta, u = BN_eval(conv + bias) from the raw output and the
+ *   running statistics (no division by gamma) and df the pool / ReLU-routed cotangent, dgamma = sum df u, dbeta = sum df.
+ *   dfilm: dev [B][n_sub*192], per band [gamma1(32) beta1(32) gamma2(64) beta2(64)]; a call WRITES its layer's slots and
+ *   leaves the other layer's alone.  Fixed-order sums (order-independent accumulators): bit-reproducible.
  * conv2 input gradient: mst_encoder_train_conv2_dgrad with drop1_mask = NULL.
  * mst_encoder_conv1_dgrad: dy1 dev [n_sub][B][32][split_size][frames] -> dlogmel dev [B][8][n_mels][frames]: per band
  *   the 7x7 convolution with the transposed, flipped conv1 weights on the band's own rows (exact-fp32 MFMA), then the
@@ -373,6 +378,9 @@ int mst_encoder_forward_frozen(const mst_encoder* enc, const float* logmel, int 
 int mst_encoder_frozen_backward_apply(const mst_encoder* enc, int layer, int B, int frames, const float* dpool,
                                       long long dp_clip, long long dp_band, long long dp_ch, float* dy, void* workspace,
                                       size_t workspace_bytes, void* stream);
+int mst_encoder_frozen_film_grad(const mst_encoder* enc, int layer, int B, int frames, const float* dpool,
+                                 long long dp_clip, long long dp_band, long long dp_ch, float* dfilm, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 int mst_encoder_conv1_dgrad(const mst_encoder* enc, const float* dy1, int B, int frames, float* dlogmel, void* workspace,
                             size_t workspace_bytes, void* stream);
 
@@ -456,7 +464,8 @@ int mst_dropout_mask(float p, uint64_t seed, long long n, unsigned char* keep, v
 
 /* FiLM MLP = MixingFeatureEncoder.forward (src/model.py:410-464) in training mode:
  * film = head(ReLU(mlp3(Dropout(ReLU(mlp0 feats)))));  feats: dev [B][feature_dim];  film: dev [B][out_dim] (n_sub * 192).
- * mst_film_backward: dfilm [B][out_dim] -> the six parameter gradients (overwritten); the features get no gradient.      */
+ * mst_film_backward: dfilm [B][out_dim] -> the six parameter gradients (overwritten); the features get no gradient here
+ * (mst_film_input_grad below: eval mode).                                                                               */
 typedef struct mst_film_dims { int32_t feature_dim, hidden, out_dim; } mst_film_dims;                /* feature_dim, hidden <= 2048 */
 typedef struct mst_film_weights {
   const float *mlp0_w, *mlp0_b;   /* feature_mlp.0 [H][Fd], [H] */
@@ -471,6 +480,11 @@ int mst_film_forward_train(const mst_film_dims* dims, const mst_film_weights* w,
 int mst_film_backward(const mst_film_dims* dims, const mst_film_weights* w, const float* feats, int B, float drop_p,
                       const float* dfilm, const void* save, const mst_film_grads* grads, void* workspace,
                       size_t workspace_bytes, void* stream);
+/* Gradient to the INPUT of the FiLM MLP, eval mode (no Dropout): dfilm [B][out_dim] -> dfeats [B][feature_dim] (overwritten)
+ * through head -> ReLU -> mlp3 -> ReLU -> mlp0; the hidden activations are recomputed from feats.  Fixed-order split sums. */
+size_t mst_film_input_grad_workspace_bytes(const mst_film_dims* dims, int B);
+int mst_film_input_grad(const mst_film_dims* dims, const mst_film_weights* w, const float* feats, int B, const float* dfilm,
+                        float* dfeats, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Song-identity discriminator of the adversarial branch = SongIdentityDiscriminator.forward (src/model.py:545-587):
  * h1 = Dropout(ReLU(w0 x + b0));  h2 = Dropout(ReLU(w3 h1 + b3));  pred = w6 h2 + b6.   x: dev [B][in_dim];  pred: dev [B][out_dim].
@@ -565,6 +579,27 @@ int mst_logmel_backward(const float* x, const float* grad_logmel, int rows, int 
                         const float* window, const int32_t* band, const float* band_weight, int band_width,
                         const int32_t* mel_ranges, float* grad_x, int accumulate, void* workspace,
                         size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Stage A backward, second path: the gradient of the MIXING FEATURES to the waveform (the reference extracts the features
+ * of the mixer's output with gradients: src/train_style_transfer.py:204-215).  Basic 64-feature layout only; of those the
+ * reference differentiates 24: per stem block o in {0 bass, 15 drums, 34 other, 49 vocals} rms L/R (o, o+1), crest L/R
+ * (o+2, o+3), rel_loudness (o+6), and the masking features 30..33; every other entry of grad_feats is ignored.
+ * x: dev fp32 [B][8][T] packed (rows vL vR bL bR dL dR oL oR); grad_feats, feats: dev fp32 [B][64], feats = the forward's
+ * values: an entry with |feats| >= 100 (clamped) or NaN passes no gradient.  grad_logmel: NULL, or dev fp32
+ * [B*8][n_mels][F] -- the log-mel cotangent of the same backward, which then rides in the SAME adjoint pass
+ * (w = g_L / (mel + 1e-10) + g_P).  Tables and parameter limits as mst_logmel_backward.
+ * A channel with sum x^2 == 0 gets exact zeros from its own rms / crest / loudness terms (the reference: NaN).
+ * grad_x: dev [B][8][T], written (accumulate = 0) or added to.  After the call the first B*8*n_mels*F floats of the
+ * workspace hold the recomputed mel power [B*8][n_mels][F].
+ * Bit-reproducible (fixed summation order, no floating-point atomics), a clip's result does not depend on its batch
+ * neighbours; stream-ordered, no host sync, no allocation.  Returns MST_EINVAL naming the reason for anything else.
+ * ------------------------------------------------------------------------------------------ */
+size_t mst_melfeat_backward_workspace_bytes(int B, int T, int n_fft, int hop, int n_mels);
+int mst_melfeat_backward(const float* x, const float* grad_feats, const float* feats, const float* grad_logmel, int B, int T,
+                         int n_fft, int hop, int n_mels, int feature_dim, const float* window, const int32_t* band,
+                         const float* band_weight, int band_width, const int32_t* mel_ranges, float* grad_x, int accumulate,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Stage C: TCN mixer (eval) -- the style-transfer stage that consumes the embeddings.

@@ -170,6 +170,9 @@ SYMBOLS = {
                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mst_film_backward": (C.c_int, [C.POINTER(FilmDims), C.POINTER(FilmPtrs), C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                     C.POINTER(FilmPtrs), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mst_film_input_grad_workspace_bytes": (C.c_size_t, [C.POINTER(FilmDims), C.c_int]),
+    "mst_film_input_grad": (C.c_int, [C.POINTER(FilmDims), C.POINTER(FilmPtrs), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_size_t, C.c_void_p]),
     "mst_disc_save_bytes": (C.c_size_t, [C.POINTER(DiscDims), C.c_int]),
     "mst_disc_backward_workspace_bytes": (C.c_size_t, [C.POINTER(DiscDims), C.c_int]),
     "mst_disc_forward": (C.c_int, [C.POINTER(DiscDims), C.POINTER(DiscPtrs), C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_uint64,
@@ -207,6 +210,8 @@ SYMBOLS = {
                                              C.POINTER(EncoderTaps), C.c_void_p, C.c_size_t, C.c_void_p]),
     "mst_encoder_frozen_backward_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_longlong,
                                                     C.c_longlong, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mst_encoder_frozen_film_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_longlong,
+                                               C.c_longlong, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mst_encoder_conv1_dgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                           C.c_void_p]),
     "mst_aug_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
@@ -230,6 +235,10 @@ SYMBOLS = {
     "mst_logmel_backward_workspace_bytes": (C.c_size_t, [C.c_int]),
     "mst_logmel_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mst_melfeat_backward_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mst_melfeat_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
     "mst_tcn_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(TcnConfig), C.POINTER(TcnWeights)]),
     "mst_tcn_destroy": (None, [C.c_void_p]),
     "mst_tcn_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_longlong]),

@@ -3837,6 +3837,58 @@ __global__ __launch_bounds__(256) void frozen_bwd_kernel(const ApplyBwdParams p,
   }
 }
 
+// ---- frozen encoder: gradient to the FiLM tensor (the mixing features are differentiated: DESIGN 3.13).  With z = gamma u + beta,
+// u = BN_eval(conv + bias) = s yraw + t (s, t: the handle's eval fold of the running statistics and the convolution bias -- no
+// division by gamma) and df as above:  dgamma[clip][band][ch] = sum df u,  dbeta = sum df.  The sums are apply_bwd_reduce_kernel's:
+// per lane in a fixed order, the four lane groups of a channel by shuffles, then the order-independent accumulators.
+template <int LAYER, int SUB>
+__global__ __launch_bounds__(256) void frozen_film_grad_kernel(const ApplyBwdParams p, const float* __restrict__ es,
+                                                               const float* __restrict__ et) {   // grid (chunks, B*nsub)
+  using C = CC<LAYER, SUB>;
+  constexpr int NT = C::NT, NV = 4 * C::MT;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int clip = blockIdx.y / p.nsub, band = blockIdx.y % p.nsub;
+  const int wus = p.tiles_r * p.tiles_c * NT;
+  const int per = ((wus + p.chunks - 1) / p.chunks + 3) & ~3;  // multiple of 4: a wave keeps its N-tile
+  const int w0 = blockIdx.x * per, w1 = min(wus, w0 + per);
+  const int j = lane & 15, g = lane >> 4;
+  float dgam = 0.f, dbet = 0.f;
+  int ch = 0;
+  for (int wu = w0 + wave; wu < w1; wu += 4) {
+    const int n = wu % NT, tile = wu / NT, tc = tile % p.tiles_c, tr = tile / p.tiles_c;
+    ch = n * 16 + j;
+    const float2 ac = p.aff[((size_t)clip * p.nsub + band) * C::COUT + ch];
+    const float s = es[band * C::COUT + ch], t = et[band * C::COUT + ch];
+    const size_t u = ((((size_t)clip * p.nsub + band) * p.tiles_r + tr) * p.tiles_c + tc) * NT + n;
+    float v[NV], df[NV];
+    load_unit<NV>(p.yraw, nullptr, band, u * 64 + lane, v);
+    unit_df<LAYER, SUB>(p, v, ac, clip, band, ch, tr, tc, g, df);
+#pragma unroll
+    for (int e = 0; e < NV; ++e) {
+      int row, col;
+      unit_geometry<LAYER, SUB>(tr, tc, g, e, row, col);
+      const float uu = (row < p.rows && col < p.cols) ? fmaf(s, v[e], t) : 0.f;   // padding slots: df is 0 there, keep 0 * x finite
+      dgam = fmaf(df[e], uu, dgam);
+      dbet += df[e];
+    }
+  }
+  dgam += __shfl_xor(dgam, 16, 64), dgam += __shfl_xor(dgam, 32, 64);
+  dbet += __shfl_xor(dbet, 16, 64), dbet += __shfl_xor(dbet, 32, 64);
+  if (lane < 16 && w0 + wave < w1) {
+    mst::DetAcc* fl = p.dfilm_acc + ((size_t)clip * p.nsub + band) * 192;
+    mst::det_add(fl + p.goff + ch, (double)dgam);
+    mst::det_add(fl + p.boff + ch, (double)dbet);
+  }
+}
+// dfilm[clip][band][goff + ch] = gamma gradient, [boff + ch] = beta gradient of this layer (written, single writer per element)
+__global__ void dfilm_store_kernel(const mst::DetAcc* acc, float* dfilm, int n192, int goff, int boff, int cout) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;   // over B * nsub * 2 * cout
+  if (i >= n192 / 192 * 2 * cout) return;
+  const int cb = i / (2 * cout), r = i % (2 * cout);
+  const int slot = r < cout ? goff + r : boff + (r - cout);
+  dfilm[(size_t)cb * 192 + slot] = (float)mst::det_get(acc[(size_t)cb * 192 + slot]);
+}
+
 // d logmel[clip][ci][mel][frame] = the bands' input gradients dxb[clip][band][ci][mel - band * overlap][frame] added in
 // ASCENDING band order (one thread per element: no atomics, the same bits every time); a mel row no band covers gets 0
 __global__ __launch_bounds__(256) void band_fold_kernel(const float* __restrict__ dxb, float* __restrict__ dlm, long long total,
@@ -4934,7 +4986,7 @@ int mst_encoder_train_conv2_dgrad(const mst_encoder* e, const float* dy2, int B,
 namespace {
 struct FrozenLayout {
   WsLayout base;
-  size_t y1, y2, stats, dxb, total;
+  size_t y1, y2, stats, dxb, facc, total;
   int tr1, tc1, tr2, tc2;
 };
 FrozenLayout frozen_layout(const mst_encoder* e, int B, int frames) {
@@ -4954,6 +5006,7 @@ FrozenLayout frozen_layout(const mst_encoder* e, int B, int frames) {
   F.y2 = take((size_t)B * ns * F.tr2 * F.tc2 * 4 * 64 * 16 * 4);
   F.stats = take((size_t)ns * 64 * 2 * sizeof(mst::DetAcc));   // the raw kernels' batch sums: written, never read
   F.dxb = take((size_t)B * ns * 8 * e->cfg.split_size * frames * 4);   // conv1 input gradient per band, before the band fold
+  F.facc = take((size_t)B * ns * 192 * sizeof(mst::DetAcc));           // FiLM-gradient accumulators (mst_encoder_frozen_film_grad)
   F.total = o;
   return F;
 }
@@ -5074,6 +5127,42 @@ int mst_encoder_frozen_backward_apply(const mst_encoder* e, int layer, int B, in
   if (layer == 1 && e->sub == 2) hipLaunchKernelGGL((frozen_bwd_kernel<1, 2>), gd, dim3(256), 0, st, p, units);
   else if (layer == 1) hipLaunchKernelGGL((frozen_bwd_kernel<1, 1>), gd, dim3(256), 0, st, p, units);
   else hipLaunchKernelGGL((frozen_bwd_kernel<2, 2>), gd, dim3(256), 0, st, p, units);
+  MST_HIP_CHECK(hipGetLastError());
+  return MST_OK;
+}
+
+int mst_encoder_frozen_film_grad(const mst_encoder* e, int layer, int B, int frames, const float* dpool, long long dp_clip,
+                                 long long dp_band, long long dp_ch, float* dfilm, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+  MST_REQUIRE(e && dpool && dfilm && (layer == 1 || layer == 2), "mst_encoder_frozen_film_grad: bad arguments");
+  FrozenLayout F;
+  if (const int rc = frozen_check("mst_encoder_frozen_film_grad", e, B, frames, workspace, workspace_bytes, &F)) return rc;
+  const WsLayout& L = F.base;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  char* ws = reinterpret_cast<char*>(workspace);
+  const int ns = e->cfg.n_subbands;
+  ApplyBwdParams p{};
+  p.dpool = dpool, p.dp_clip = dp_clip, p.dp_band = dp_band, p.dp_ch = dp_ch;
+  p.B = B, p.nsub = ns, p.pool_h = e->sub;
+  p.dfilm_acc = reinterpret_cast<mst::DetAcc*>(ws + F.facc);
+  MST_HIP_CHECK(hipMemsetAsync(p.dfilm_acc, 0, (size_t)B * ns * 192 * sizeof(mst::DetAcc), st));
+  if (layer == 1) {
+    p.yraw = reinterpret_cast<const float*>(ws + F.y1), p.aff = reinterpret_cast<const float2*>(ws + L.aff1);
+    p.dp_rows = e->H1, p.dp_cols = L.W1, p.tiles_r = F.tr1, p.tiles_c = F.tc1;
+    p.rows = e->cfg.split_size, p.cols = frames, p.goff = 0, p.boff = 32;
+  } else {
+    p.yraw = reinterpret_cast<const float*>(ws + F.y2), p.aff = reinterpret_cast<const float2*>(ws + L.aff2);
+    p.dp_rows = e->FD, p.dp_cols = L.W2, p.tiles_r = F.tr2, p.tiles_c = F.tc2;
+    p.rows = e->H1, p.cols = L.W1, p.goff = 64, p.boff = 128;
+  }
+  const int cout = layer == 1 ? 32 : 64, wus = p.tiles_r * p.tiles_c * (layer == 1 ? 2 : 4);
+  p.chunks = std::max(1, std::min(16, wus / 64));
+  const dim3 gr(p.chunks, B * ns);
+  if (layer == 1 && e->sub == 2) hipLaunchKernelGGL((frozen_film_grad_kernel<1, 2>), gr, dim3(256), 0, st, p, e->s1, e->t1);
+  else if (layer == 1) hipLaunchKernelGGL((frozen_film_grad_kernel<1, 1>), gr, dim3(256), 0, st, p, e->s1, e->t1);
+  else hipLaunchKernelGGL((frozen_film_grad_kernel<2, 2>), gr, dim3(256), 0, st, p, e->s2, e->t2);
+  hipLaunchKernelGGL(dfilm_store_kernel, dim3((B * ns * 2 * cout + 255) / 256), dim3(256), 0, st, p.dfilm_acc, dfilm, B * ns * 192, p.goff,
+                     p.boff, cout);
   MST_HIP_CHECK(hipGetLastError());
   return MST_OK;
 }

@@ -545,6 +545,41 @@ int mst_film_backward(const mst_film_dims* dm, const mst_film_weights* w, const 
   return MST_OK;
 }
 
+// Gradient to the INPUT of the FiLM MLP in eval mode (no Dropout): dfilm [B][O] -> dfeats [B][Fd] through head -> ReLU ->
+// mlp3 -> ReLU -> mlp0.  The two hidden activations are recomputed from `feats` (B x H each); every product is split-K with a
+// fixed-order sum, as in mst_film_backward.  Workspace: h1, h2, dh2, dh1 and the partial sums.
+size_t mst_film_input_grad_workspace_bytes(const mst_film_dims* d, int B) {
+  if (!d || B <= 0) return 0;
+  return ((size_t)4 * B * d->hidden + (size_t)kSplitFilm * B * std::max(d->hidden, d->feature_dim)) * sizeof(float);
+}
+
+int mst_film_input_grad(const mst_film_dims* dm, const mst_film_weights* w, const float* feats, int B, const float* dfilm, float* dfeats,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  MST_REQUIRE(dm && w && feats && dfilm && dfeats && workspace && B > 0, "mst_film_input_grad: NULL / bad argument");
+  MST_REQUIRE(w->mlp0_w && w->mlp0_b && w->mlp3_w && w->mlp3_b && w->head_w && w->head_b, "mst_film_input_grad: NULL weight");
+  const int Fd = dm->feature_dim, H = dm->hidden, O = dm->out_dim;
+  MST_REQUIRE(Fd >= 1 && Fd <= 2048 && H >= 1 && H <= 2048 && O >= 1, "mst_film_input_grad: dims out of range (feature_dim=%d hidden=%d out_dim=%d; limits 2048, 2048)", Fd, H, O);
+  const size_t need = mst_film_input_grad_workspace_bytes(dm, B);
+  if (workspace_bytes < need) return mst::fail(MST_ENOMEM, "mst_film_input_grad: workspace %zu B < required %zu B", workspace_bytes, need);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  float* h1 = static_cast<float*>(workspace);
+  float* h2 = h1 + (size_t)B * H;
+  float* dh2 = h2 + (size_t)B * H;
+  float* dh1 = dh2 + (size_t)B * H;
+  float* part = dh1 + (size_t)B * H;
+  auto linear = [&](const float* X, const float* W, const float* bias, float* out, int N, int K) {   // out = ReLU(X W^T + b)
+    hipLaunchKernelGGL((gemm_kernel<false, false, RowMajA, RowMajT, LinEpi>), dim3((N + 63) / 64, (B + 63) / 64, 1), dim3(256), 0, st, B, N, K, 1,
+                       round_up(K, kKC), RowMajA{X, K}, RowMajT{W, K}, LinEpi{out, bias, N, 1, make_drop(0.f, 0)});
+  };
+  linear(feats, w->mlp0_w, w->mlp0_b, h1, H, Fd);
+  linear(h1, w->mlp3_w, w->mlp3_b, h2, H, H);
+  gemm_split<false, true>(B, H, O, kSplitFilm, RowMajA{dfilm, O}, RowMajB{w->head_w, H}, part, FinMask{dh2, h2, 1.f}, st);
+  gemm_split<false, true>(B, H, H, 2, RowMajA{dh2, H}, RowMajB{w->mlp3_w, H}, part, FinMask{dh1, h1, 1.f}, st);
+  gemm_split<false, true>(B, Fd, H, 2, RowMajA{dh1, H}, RowMajB{w->mlp0_w, Fd}, part, FinStore{dfeats}, st);
+  MST_HIP_CHECK(hipGetLastError());
+  return MST_OK;
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------

@@ -477,7 +477,7 @@ constexpr size_t kMaxLds = 160 * 1024;
 
 struct LogmelBwdParams {
   const float* x;        // [rows][T]
-  const float* g;        // [rows][n_mels][F] cotangent on the log-mel
+  const float* g;        // [rows][n_mels][F] cotangent on the log-mel (kPower: on the mel POWER, used as w as it stands)
   const float* window;
   const int2* band;      // [N / 2 + 1] (first mel index, count <= kBandMax)
   const float2* bandw;   // [N / 2 + 1] weights of (first, first + 1), zero where absent
@@ -487,7 +487,41 @@ struct LogmelBwdParams {
   int rows, T, hop, lh, R, F, nchunks, cpb, blocks_per_row, accumulate, n_mels, wstride;
 };
 
+// Mel power of the two frames of a pair, as the log-mel backward recomputes it: every bin lays out its power times its two mel
+// weights, one lane per mel adds up the bins of its triangle (rising half: bins whose second mel it is; falling half: bins whose
+// first) in bin order.  Uses the wave's scratch; the caller fences before the scratch is written again.
 template <int N>
+__device__ __forceinline__ void mel_power_pair(const float2 (&XA)[Geo<N>::NB], const float2 (&XB)[Geo<N>::NB], const float2* __restrict__ bandw,
+                                               const int4 (&mr)[kMelRounds], int n_mels, const Lds<N>& l, int lane,
+                                               float (&sa)[kMelRounds], float (&sb)[kMelRounds]) {
+  using G = Geo<N>;
+  float4* Q = reinterpret_cast<float4*>(l.scr);   // per bin (w0 P_A, w0 P_B, w1 P_A, w1 P_B): the power spectrum times its two mel weights
+#pragma unroll
+  for (int j = 0; j < G::NB; ++j) {
+    const int k = j == G::NB - 1 ? N / 2 : lane + 64 * j;
+    const float2 bw = bandw[k];
+    const float pa = fmaf(XA[j].x, XA[j].x, XA[j].y * XA[j].y), pb = fmaf(XB[j].x, XB[j].x, XB[j].y * XB[j].y);
+    if (j < G::NB - 1 || lane == 0) Q[k] = make_float4(bw.x * pa, bw.x * pb, bw.y * pa, bw.y * pb);
+  }
+  wsync();
+#pragma unroll
+  for (int q = 0; q < kMelRounds; ++q) {
+    sa[q] = sb[q] = 0.f;
+    if (lane + 64 * q < n_mels) {
+      for (int i = 0; i < mr[q].w; ++i) {
+        const float4 t = Q[mr[q].z + i];
+        sa[q] += t.z, sb[q] += t.w;
+      }
+      for (int i = 0; i < mr[q].y; ++i) {
+        const float4 t = Q[mr[q].x + i];
+        sa[q] += t.x, sb[q] += t.y;
+      }
+    }
+  }
+}
+
+// kPower: the cotangent arrives on the mel POWER (w = g, nothing recomputed but the spectra) -- mst_melfeat_backward
+template <int N, bool kPower>
 __global__ __launch_bounds__(kThreads) void logmel_bwd_kernel(const LogmelBwdParams p) {
   using G = Geo<N>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -500,7 +534,6 @@ __global__ __launch_bounds__(kThreads) void logmel_bwd_kernel(const LogmelBwdPar
   float* behind = l.acc + G::ring(R, hop);
   float2* wv = reinterpret_cast<float2*>(behind + G::kWv) + wave * kMelMax;   // this wave's w = g / (mel + 1e-10), frames (A, B)
   float* gt = behind + G::kGt;   // cotangent tile of this workgroup's frames, [n_mels][wstride]
-  float4* Q = reinterpret_cast<float4*>(l.scr);   // per bin (w0 P_A, w0 P_B, w1 P_A, w1 P_B): the power spectrum times its two mel weights
   const int row = blockIdx.x / p.blocks_per_row, blk = blockIdx.x % p.blocks_per_row;
   const int c0 = blk * p.cpb, c1 = min(c0 + p.cpb, p.nchunks);
   const int fa = max(0, c0 - R + 1), fb = min(p.F - 1, c1 - 1);
@@ -533,32 +566,22 @@ __global__ __launch_bounds__(kThreads) void logmel_bwd_kernel(const LogmelBwdPar
       load_pair<N>(xr, p.T, start, hop, hasB, l, v, lane);
       wave_fft<N>(v, l, lane);
       split_pair<N>(v, l, lane, XA, XB);
-      // mel power of the two frames, recomputed: every bin lays out its power times its two mel weights, one lane per mel adds
-      // up the bins of its triangle (rising half: bins whose second mel it is; falling half: bins whose first) in bin order
-#pragma unroll
-      for (int j = 0; j < G::NB; ++j) {
-        const int k = j == G::NB - 1 ? N / 2 : lane + 64 * j;
-        const float2 bw = p.bandw[k];
-        const float pa = fmaf(XA[j].x, XA[j].x, XA[j].y * XA[j].y), pb = fmaf(XB[j].x, XB[j].x, XB[j].y * XB[j].y);
-        if (j < G::NB - 1 || lane == 0) Q[k] = make_float4(bw.x * pa, bw.x * pb, bw.y * pa, bw.y * pb);
-      }
-      wsync();
+      // w of the two frames: g / (mel + 1e-10) with the mel power recomputed, or g itself (cotangent on the power)
       const float* ga = gt + (gA - fa);
       const float* gb = ga + (hasB ? 1 : 0);   // (no second frame: no read past the tile)
+      if constexpr (kPower) {
 #pragma unroll
-      for (int q = 0; q < kMelRounds; ++q) {
-        const int m = lane + 64 * q;
-        if (m < p.n_mels) {
-          float sa = 0.f, sb = 0.f;
-          for (int i = 0; i < mr[q].w; ++i) {
-            const float4 t = Q[mr[q].z + i];
-            sa += t.z, sb += t.w;
-          }
-          for (int i = 0; i < mr[q].y; ++i) {
-            const float4 t = Q[mr[q].x + i];
-            sa += t.x, sb += t.y;
-          }
-          wv[m] = make_float2(ga[m * ws] / (sa + 1e-10f), gb[m * ws] / (sb + 1e-10f));
+        for (int q = 0; q < kMelRounds; ++q) {
+          const int m = lane + 64 * q;
+          if (m < p.n_mels) wv[m] = make_float2(ga[m * ws], gb[m * ws]);
+        }
+      } else {
+        float sa[kMelRounds], sb[kMelRounds];
+        mel_power_pair<N>(XA, XB, p.bandw, mr, p.n_mels, l, lane, sa, sb);
+#pragma unroll
+        for (int q = 0; q < kMelRounds; ++q) {
+          const int m = lane + 64 * q;
+          if (m < p.n_mels) wv[m] = make_float2(ga[m * ws] / (sa[q] + 1e-10f), gb[m * ws] / (sb[q] + 1e-10f));
         }
       }
       wsync();
@@ -638,7 +661,7 @@ __global__ __launch_bounds__(kThreads) void logmel_bwd_kernel(const LogmelBwdPar
 // row pitch of the cotangent tile: the cpb + R - 1 frames a workgroup reads, made odd
 int wstride_of(int cpb, int R) { return (cpb + R - 1) | 1; }
 
-template <int N>
+template <int N, bool kPower = false>
 int launch_logmel_bwd(LogmelBwdParams& p, hipStream_t st) {
   // a workgroup owns 64 hop-sized chunks; fewer where the cotangent tile of 64 + R - 1 frames would not fit the CU's LDS next to
   // the transform's tables (n_fft = 2048 with more than ~118 mels)
@@ -651,7 +674,7 @@ int launch_logmel_bwd(LogmelBwdParams& p, hipStream_t st) {
   p.blocks_per_row = (p.nchunks + p.cpb - 1) / p.cpb;
   const long long grid = (long long)p.rows * p.blocks_per_row;
   MST_REQUIRE(grid < (1LL << 31), "mst_logmel_backward: %lld workgroups", grid);
-  MST_HIP_CHECK(mst::launch_lds<logmel_bwd_kernel<N>>(dim3((unsigned)grid), dim3(kThreads), lds, st, p));
+  MST_HIP_CHECK(mst::launch_lds<logmel_bwd_kernel<N, kPower>>(dim3((unsigned)grid), dim3(kThreads), lds, st, p));
   return MST_OK;
 }
 
@@ -691,6 +714,330 @@ int mst_logmel_backward(const float* x, const float* grad_logmel, int rows, int 
   p.accumulate = accumulate != 0, p.n_mels = n_mels;
   p.cpb = p.blocks_per_row = p.wstride = 0;
   if (int rc = n_fft == 1024 ? launch_logmel_bwd<1024>(p, st) : launch_logmel_bwd<2048>(p, st)) return rc;
+  hipLaunchKernelGGL(mrstft_fold_kernel, dim3(rows), dim3(256), 0, st, grad_x, p.border, T, n_fft / 2);
+  MST_HIP_CHECK(hipGetLastError());
+  return MST_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Mixing features: gradient to the waveform (mst_melfeat_backward).  Of the 64 features of the default layout 24 carry a
+// gradient in the reference (the rest are rebuilt from Python numbers there): per stem rms L/R, crest L/R and rel_loudness --
+// functions of a few per-channel scalars (sum x^2, the first arg-max of |x|, sum mix^2) -- and the four masking features,
+// means of sigmoid(max_{k != i} S_k - S_i) over the mel power S (channel mean) of the four stems.
+//   1. scalars: per channel (8 stem channels + 2 mixture channels of a clip) 32 segments, one workgroup each, fixed-order
+//      double sums; the segments are combined in ascending order where the coefficients are formed;
+//   2. coefficients: grad = a_row x + m_ch mix + spike at t* -- a_row, m_ch, spike in double per clip;
+//   3. one elementwise pass writes (or accumulates) that;
+//   4. the mel power of all 8 rows is recomputed into the workspace (mel_power_pair: the log-mel backward's arithmetic),
+//   5. one thread per (clip, mel, frame) turns it into the cotangent on the mel power of the 8 rows, plus the log-mel
+//      cotangent g_L / (mel + 1e-10) when one arrives in the same backward,
+//   6. and the log-mel backward's adjoint stage (logmel_bwd_kernel<N, true>) adds its waveform gradient: ONE adjoint pass.
+// A feature whose forward value sits on the clamp (|f| >= 100) or is not finite passes no gradient; a channel with sum x^2 = 0
+// gets exact zeros from its own rms / crest / loudness terms (the reference: NaN from sqrt'(0) 0).
+namespace {
+
+constexpr int kFeatDim = 64;         // default (basic) layout
+constexpr int kScalarThreads = 256, kScalarSegs = 32;   // a channel's samples: 32 segments, one workgroup each
+// offsets of the per-stem blocks in the feature vector (keys sorted: bass, drums, masking, other, vocals), rows are v, b, d, o
+__device__ __constant__ int kStemOff[4] = {49, 0, 15, 34};
+constexpr int kMaskOff = 30;         // masking: vocals, bass, drums, other
+
+struct ChanScalars {   // of one channel (or mixture channel)
+  double ss;           // sum x^2
+  float xpeak;         // x[t*]
+  int tstar;           // first index of max |x|
+};
+struct RowCoef {
+  double a, spike;     // grad[t] = a x[t] + mixc[ch] mix[t] + (t == tstar) spike
+  int tstar, pad_;
+};
+
+__device__ __forceinline__ float live_cot(const float* g, const float* f, int i) {   // cotangent of feature i, 0 where clamped / NaN
+  return fabsf(f[i]) < 100.f ? g[i] : 0.f;
+}
+__device__ __forceinline__ float mix_at(const float* xc, int ch, int T, int t) {   // sum(stems.values()): ((v + b) + d) + o
+  return ((xc[(size_t)ch * T + t] + xc[(size_t)(2 + ch) * T + t]) + xc[(size_t)(4 + ch) * T + t]) + xc[(size_t)(6 + ch) * T + t];
+}
+
+// grid (kScalarSegs, B * 10): segment of channel r < 8 of the clip, or of mixture channel r - 8 -> out[channel][segment]
+__global__ __launch_bounds__(kScalarThreads) void melfeat_scalars_kernel(const float* __restrict__ x, int T, ChanScalars* __restrict__ out) {
+  __shared__ double ssum[kScalarThreads];
+  __shared__ float sabs[kScalarThreads];
+  __shared__ float sval[kScalarThreads];
+  __shared__ int sidx[kScalarThreads];
+  const int b = blockIdx.y / 10, r = blockIdx.y % 10, tid = threadIdx.x;
+  const int len = (T + kScalarSegs - 1) / kScalarSegs, t0 = blockIdx.x * len, t1 = min(T, t0 + len);
+  const float* xc = x + (size_t)b * 8 * T;
+  double ss = 0.0;
+  float best = -1.f, bval = 0.f;
+  int bidx = t0;
+  for (int t = t0 + tid; t < t1; t += kScalarThreads) {
+    const float v = r < 8 ? xc[(size_t)r * T + t] : mix_at(xc, r - 8, T, t);
+    ss += (double)v * (double)v;
+    if (fabsf(v) > best) best = fabsf(v), bval = v, bidx = t;   // (strictly greater: the first index of this thread's samples)
+  }
+  ssum[tid] = ss, sabs[tid] = best, sval[tid] = bval, sidx[tid] = bidx;
+  __syncthreads();
+  for (int o = kScalarThreads / 2; o > 0; o >>= 1) {
+    if (tid < o) {
+      ssum[tid] += ssum[tid + o];
+      const bool take = sabs[tid + o] > sabs[tid] || (sabs[tid + o] == sabs[tid] && sidx[tid + o] < sidx[tid]);
+      if (take) sabs[tid] = sabs[tid + o], sval[tid] = sval[tid + o], sidx[tid] = sidx[tid + o];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    ChanScalars s;
+    s.ss = ssum[0], s.xpeak = sval[0], s.tstar = sidx[0];
+    out[(size_t)blockIdx.y * kScalarSegs + blockIdx.x] = s;
+  }
+}
+// a channel's segments in ascending order: the sum in a fixed order, the FIRST arg-max (strictly greater moves it)
+__device__ __forceinline__ ChanScalars chan_scalars(const ChanScalars* __restrict__ seg) {
+  ChanScalars s = seg[0];
+  for (int k = 1; k < kScalarSegs; ++k) {
+    s.ss += seg[k].ss;
+    if (fabsf(seg[k].xpeak) > fabsf(s.xpeak)) s.xpeak = seg[k].xpeak, s.tstar = seg[k].tstar;
+  }
+  return s;
+}
+
+// grid B, 64 threads: lanes 0..7 the rows' coefficients, lanes 8, 9 the mixture channels'
+__global__ __launch_bounds__(64) void melfeat_coef_kernel(const ChanScalars* __restrict__ sc, const float* __restrict__ g,
+                                                          const float* __restrict__ feats, int T, RowCoef* __restrict__ coef,
+                                                          double* __restrict__ mixc) {
+  const int b = blockIdx.x, r = threadIdx.x;
+  __shared__ ChanScalars s[10];
+  if (r < 10) s[r] = chan_scalars(sc + ((size_t)b * 10 + r) * kScalarSegs);
+  __syncthreads();
+  const float* gb = g + (size_t)b * kFeatDim;
+  const float* fb = feats + (size_t)b * kFeatDim;
+  const double kLog = 10.0 / 2.302585092994045684, dT = (double)T;
+  if (r < 8) {
+    const int i = r >> 1, c = r & 1, o = kStemOff[i];
+    const double ss = s[r].ss, rms = sqrt(ss / dT);
+    const double g_rms = live_cot(gb, fb, o + c), g_crest = live_cot(gb, fb, o + 2 + c), g_rel = live_cot(gb, fb, o + 6);
+    RowCoef k;
+    k.a = k.spike = 0.0, k.tstar = s[r].tstar, k.pad_ = 0;
+    if (ss > 0.0) {
+      const double peak = fabs((double)s[r].xpeak);
+      const double mean2 = (s[2 * i].ss + s[2 * i + 1].ss) / (2.0 * dT);
+      k.a = g_rms / (dT * rms) - g_crest * 2.0 * kLog / (dT * rms * (rms + 1e-8)) + g_rel * kLog / (dT * (mean2 + 1e-10));
+      k.spike = g_crest * 2.0 * kLog * (s[r].xpeak > 0.f ? 1.0 : -1.0) / peak;
+      if (!isfinite(k.a)) k.a = 0.0;
+      if (!isfinite(k.spike)) k.spike = 0.0;
+    }
+    coef[(size_t)b * 8 + r] = k;
+  } else if (r < 10) {
+    double gs = 0.0;
+    for (int i = 0; i < 4; ++i) gs += (double)live_cot(gb, fb, kStemOff[i] + 6);
+    const double mean2 = (s[8].ss + s[9].ss) / (2.0 * dT);
+    const double m = -gs * kLog / (dT * (mean2 + 1e-10));
+    mixc[(size_t)b * 2 + (r - 8)] = isfinite(m) ? m : 0.0;
+  }
+}
+
+// grid (blocks along T, B * 8)
+__global__ __launch_bounds__(256) void melfeat_time_kernel(const float* __restrict__ x, int T, const RowCoef* __restrict__ coef,
+                                                           const double* __restrict__ mixc, float* __restrict__ grad, int accumulate) {
+  const int row = blockIdx.y, b = row >> 3, r = row & 7;
+  const RowCoef k = coef[row];
+  const double m = mixc[(size_t)b * 2 + (r & 1)];
+  const float* xc = x + (size_t)b * 8 * T;
+  float* gr = grad + (size_t)row * T;
+  for (int t = blockIdx.x * 256 + threadIdx.x; t < T; t += gridDim.x * 256) {
+    double v = k.a * (double)xc[(size_t)r * T + t];
+    if (m != 0.0) v += m * (double)mix_at(xc, r & 1, T, t);
+    if (t == k.tstar) v += k.spike;
+    const float o = (float)v;
+    gr[t] = accumulate ? gr[t] + o : o;
+  }
+}
+
+struct MelpowParams {
+  const float* x;
+  const float* window;
+  const float2* bandw;
+  const int4* melr;
+  float* P;   // [rows][n_mels][F]
+  int rows, T, hop, F, pairs_per_row, n_mels;
+};
+
+template <int N>
+__global__ __launch_bounds__(kThreads) void melpow_kernel(const MelpowParams p) {
+  using G = Geo<N>;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  Lds<N> l(smem, wave);
+  l.fill(p.window, tid);
+  int4 mr[kMelRounds];
+#pragma unroll
+  for (int q = 0; q < kMelRounds; ++q) mr[q] = lane + 64 * q < p.n_mels ? p.melr[lane + 64 * q] : make_int4(0, 0, 0, 0);
+  __syncthreads();
+  const int items = p.rows * p.pairs_per_row;
+  for (int it = blockIdx.x * kWaves + wave; it < items; it += gridDim.x * kWaves) {
+    const int row = it / p.pairs_per_row, f = 2 * (it % p.pairs_per_row);
+    const bool hasB = f + 1 < p.F;
+    float2 v[G::NF][G::NCR], XA[G::NB], XB[G::NB];
+    load_pair<N>(p.x + (size_t)row * p.T, p.T, f * p.hop - N / 2, p.hop, hasB, l, v, lane);
+    wave_fft<N>(v, l, lane);
+    split_pair<N>(v, l, lane, XA, XB);
+    float sa[kMelRounds], sb[kMelRounds];
+    mel_power_pair<N>(XA, XB, p.bandw, mr, p.n_mels, l, lane, sa, sb);
+#pragma unroll
+    for (int q = 0; q < kMelRounds; ++q) {
+      const int m = lane + 64 * q;
+      if (m < p.n_mels) {
+        float* o = p.P + ((size_t)row * p.n_mels + m) * p.F + f;
+        o[0] = sa[q];
+        if (hasB) o[1] = sb[q];
+      }
+    }
+    wsync();
+  }
+}
+
+// one thread per (clip, mel, frame): P (mel power of the clip's 8 rows) -> W (cotangent on it; + g_L / (P + 1e-10))
+__global__ __launch_bounds__(256) void melfeat_cot_kernel(const float* __restrict__ P, const float* __restrict__ gl, const float* __restrict__ g,
+                                                          const float* __restrict__ feats, size_t MF, float scale, float* __restrict__ W) {
+  const int b = blockIdx.y;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= MF) return;
+  const size_t base = (size_t)b * 8 * MF + i;
+  float pv[8], S[4], c[4], cot[4];
+  int arg[4];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) pv[r] = P[base + (size_t)r * MF];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) S[s] = (pv[2 * s] + pv[2 * s + 1]) * 0.5f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float mx = -1.f;   // S >= 0; the first maximum in stem order without j, as torch.stack(...).max(0) picks
+    int am = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (k != j && S[k] > mx) mx = S[k], am = k;
+    const float sg = 1.f / (1.f + expf(S[j] - mx));
+    c[j] = live_cot(g + (size_t)b * kFeatDim, feats + (size_t)b * kFeatDim, kMaskOff + j) * (sg * (1.f - sg));
+    arg[j] = am;
+    cot[j] = 0.f;
+  }
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    float t = -c[s];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j != s && arg[j] == s) t += c[j];
+    cot[s] = scale * t;
+  }
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    float w = cot[r >> 1];
+    if (!(fabsf(w) <= 3.0e38f)) w = 0.f;   // (not finite: inputs that are not)
+    if (gl) w += gl[base + (size_t)r * MF] / (pv[r] + 1e-10f);
+    W[base + (size_t)r * MF] = w;
+  }
+}
+
+struct MelfeatBwdLayout {
+  size_t border, scalars, coef, mixc, P, W, total;
+};
+MelfeatBwdLayout melfeat_bwd_layout(int B, int n_mels, int F) {
+  MelfeatBwdLayout L;
+  size_t o = 0;
+  const size_t pf = mst::align_up((size_t)B * 8 * n_mels * F * sizeof(float), 256);
+  L.P = o, o += pf;   // first: callers (tests) may read the recomputed mel power back
+  L.W = o, o += pf;
+  L.border = o, o += mst::align_up((size_t)B * 8 * 2 * kBorder * sizeof(float), 256);
+  L.scalars = o, o += mst::align_up((size_t)B * 10 * kScalarSegs * sizeof(ChanScalars), 256);
+  L.coef = o, o += mst::align_up((size_t)B * 8 * sizeof(RowCoef), 256);
+  L.mixc = o, o += mst::align_up((size_t)B * 2 * sizeof(double), 256);
+  L.total = o;
+  return L;
+}
+
+template <int N>
+hipError_t launch_melpow(const MelpowParams& p, int grid, hipStream_t st) {
+  return mst::launch_lds<melpow_kernel<N>>(dim3(grid), dim3(kThreads), Geo<N>::kLds, st, p);
+}
+
+const char* melfeat_bwd_args(int B, int T, int n_fft, int hop, int n_mels, int feature_dim) {
+  static thread_local char why[160];
+  if (feature_dim != kFeatDim) {
+    snprintf(why, sizeof why, "feature_dim=%d: only the basic 64-feature layout is differentiated (detailed-spectral mode is not)", feature_dim);
+    return why;
+  }
+  if (n_fft != 1024 && n_fft != 2048) return snprintf(why, sizeof why, "n_fft=%d is not 1024 or 2048", n_fft), why;
+  if (hop != n_fft / 8 && hop != n_fft / 4 && hop != n_fft / 2)
+    return snprintf(why, sizeof why, "hop=%d is not n_fft/8, /4 or /2 (n_fft=%d)", hop, n_fft), why;
+  if (n_mels < 1 || n_mels > kMelMax) return snprintf(why, sizeof why, "n_mels=%d outside 1..%d", n_mels, kMelMax), why;
+  if (B <= 0 || B > (1 << 12) || T <= 0 || T >= (1 << 30)) return snprintf(why, sizeof why, "bad sizes B=%d T=%d", B, T), why;
+  if (T <= n_fft / 2) return snprintf(why, sizeof why, "T=%d needs more than n_fft/2 = %d samples (reflect padding)", T, n_fft / 2), why;
+  if ((long long)B * 8 * n_mels * (1 + T / hop) >= (1LL << 31))
+    return snprintf(why, sizeof why, "%lld mel-power values exceed 2^31", (long long)B * 8 * n_mels * (1 + T / hop)), why;
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mst_melfeat_backward_workspace_bytes(int B, int T, int n_fft, int hop, int n_mels) {
+  if (melfeat_bwd_args(B, T, n_fft, hop, n_mels, kFeatDim)) return 0;
+  return melfeat_bwd_layout(B, n_mels, 1 + T / hop).total;
+}
+
+int mst_melfeat_backward(const float* x, const float* grad_feats, const float* feats, const float* grad_logmel, int B, int T,
+                         int n_fft, int hop, int n_mels, int feature_dim, const float* window, const int32_t* band,
+                         const float* band_weight, int band_width, const int32_t* mel_ranges, float* grad_x, int accumulate,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+  MST_REQUIRE(x && grad_feats && feats && window && band && band_weight && mel_ranges && grad_x, "mst_melfeat_backward: NULL argument");
+  if (const char* why = melfeat_bwd_args(B, T, n_fft, hop, n_mels, feature_dim)) return mst::fail(MST_EINVAL, "mst_melfeat_backward: %s", why);
+  MST_REQUIRE(band_width >= 1 && band_width <= kBandMax,
+              "mst_melfeat_backward: the filterbank's widest band has %d non-zero mel weights on one bin, the kernel carries %d "
+              "(HTK triangles have 2); the table is refused, not truncated", band_width, kBandMax);
+  const int rows = B * 8, F = 1 + T / hop;
+  const MelfeatBwdLayout L = melfeat_bwd_layout(B, n_mels, F);
+  if (!workspace || workspace_bytes < L.total)
+    return mst::fail(MST_ENOMEM, "mst_melfeat_backward: workspace %zu B < required %zu B", workspace_bytes, L.total);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  char* ws = reinterpret_cast<char*>(workspace);
+  ChanScalars* sc = reinterpret_cast<ChanScalars*>(ws + L.scalars);
+  RowCoef* coef = reinterpret_cast<RowCoef*>(ws + L.coef);
+  double* mixc = reinterpret_cast<double*>(ws + L.mixc);
+  float* P = reinterpret_cast<float*>(ws + L.P);
+  float* W = reinterpret_cast<float*>(ws + L.W);
+  // time-domain terms
+  hipLaunchKernelGGL(melfeat_scalars_kernel, dim3(kScalarSegs, B * 10), dim3(kScalarThreads), 0, st, x, T, sc);
+  hipLaunchKernelGGL(melfeat_coef_kernel, dim3(B), dim3(64), 0, st, sc, grad_feats, feats, T, coef, mixc);
+  hipLaunchKernelGGL(melfeat_time_kernel, dim3(std::min((T + 255) / 256, 512), rows), dim3(256), 0, st, x, T, coef, mixc, grad_x,
+                     accumulate != 0);
+  MST_HIP_CHECK(hipGetLastError());
+  // masking (+ the log-mel cotangent): mel power of every row, cotangent on it, one adjoint pass
+  MelpowParams mp;
+  mp.x = x, mp.window = window, mp.bandw = reinterpret_cast<const float2*>(band_weight), mp.melr = reinterpret_cast<const int4*>(mel_ranges);
+  mp.P = P, mp.rows = rows, mp.T = T, mp.hop = hop, mp.F = F, mp.pairs_per_row = (F + 1) / 2, mp.n_mels = n_mels;
+  const long long items = (long long)rows * mp.pairs_per_row;
+  MST_REQUIRE(items < (1LL << 31), "mst_melfeat_backward: %lld frame pairs", items);
+  const int pgrid = (int)std::min<long long>((items + kWaves - 1) / kWaves, kFwdMaxBlocks);
+  MST_HIP_CHECK(n_fft == 1024 ? launch_melpow<1024>(mp, pgrid, st) : launch_melpow<2048>(mp, pgrid, st));
+  const size_t MF = (size_t)n_mels * F;
+  hipLaunchKernelGGL(melfeat_cot_kernel, dim3((unsigned)((MF + 255) / 256), B), dim3(256), 0, st, P, grad_logmel, grad_feats, feats, MF,
+                     (float)(1.0 / (2.0 * (double)MF)), W);
+  MST_HIP_CHECK(hipGetLastError());
+  LogmelBwdParams p;
+  p.x = x, p.g = W, p.window = window;
+  p.band = reinterpret_cast<const int2*>(band), p.bandw = reinterpret_cast<const float2*>(band_weight);
+  p.melr = reinterpret_cast<const int4*>(mel_ranges);
+  p.grad = grad_x, p.border = reinterpret_cast<float*>(ws + L.border);
+  p.rows = rows, p.T = T, p.hop = hop, p.lh = log2_exact(hop), p.R = n_fft / hop, p.F = F;
+  p.nchunks = (int)(((long long)T + n_fft + hop - 1) / hop);
+  p.accumulate = 1, p.n_mels = n_mels;
+  p.cpb = p.blocks_per_row = p.wstride = 0;
+  if (int rc = n_fft == 1024 ? launch_logmel_bwd<1024, true>(p, st) : launch_logmel_bwd<2048, true>(p, st)) return rc;
   hipLaunchKernelGGL(mrstft_fold_kernel, dim3(rows), dim3(256), 0, st, grad_x, p.border, T, n_fft / 2);
   MST_HIP_CHECK(hipGetLastError());
   return MST_OK;

@@ -113,6 +113,93 @@ def band_table_to_dense(first, count, weights, n_mels):
     return fb
 
 
+def grad_tables(window, fb, n_mels, device):
+    """The tables the stage-A backward kernels read (`mst_logmel_backward`, `mst_melfeat_backward`), on `device`:
+    (window, band (n_freqs, 2) int32, band weights (n_freqs, >= LOGMEL_BAND_MAX), width, mel_ranges (n_mels, 4) int32).
+    Raises ValueError for a filterbank whose filters are not contiguous runs of bins."""
+    first, count, weights = mel_band_table(fb)
+    width = weights.shape[1]
+    w2 = torch.zeros(weights.shape[0], max(width, LOGMEL_BAND_MAX))
+    w2[:, :width] = weights   # the kernel's row stride; a wider table is passed on as it is and refused there
+    melr = mel_bin_ranges(first, count, n_mels) if width <= LOGMEL_BAND_MAX else torch.zeros(n_mels, 4, dtype=torch.int32)
+    return (window.detach().float().to(device).contiguous(), torch.stack([first, count], dim=1).contiguous().to(device),
+            w2.contiguous().to(device), width, melr.to(device))
+
+
+# The 24 of the 64 basic features that carry a gradient to the stems in the reference (src/mixing_utils.py: the others go
+# through `.item()` or are rebuilt with `torch.tensor([...])`): per stem block rms L/R, crest L/R, rel_loudness; the masking four.
+LIVE_FEATURES = tuple(sorted([o + k for o in (0, 15, 34, 49) for k in (0, 1, 2, 3, 6)] + [30, 31, 32, 33]))
+
+
+def feature_grad_refusal(stems_dict, n_fft, hop, n_mels, detailed):
+    """Why `mst_melfeat_backward` cannot differentiate the mixing features of this call (None = it can)."""
+    if detailed:
+        return ("use_detailed_spectral=True: only the basic 64-feature layout is differentiated (the detailed-spectral curve "
+                "carries a gradient in the reference that is not built here)")
+    parts = [stems_dict[s] for s in STEMS]
+    for s, q in zip(STEMS, parts):
+        if not q.is_cuda:
+            return f"libmst kernels need CUDA (HIP) tensors and there is no CPU fallback, got '{s}' on {q.device}"
+        if q.dtype != torch.float32:
+            return f"the waveform gradient is fp32, got '{s}' of {q.dtype}"
+        if q.shape != parts[0].shape or q.dim() not in (2, 3) or q.shape[-2] != 2:
+            return f"stems of one shape (B, 2, T) or (2, T) are needed, got {[tuple(t.shape) for t in parts]}"
+    if n_fft not in (1024, 2048):
+        return f"the backward kernel has n_fft 1024 and 2048, got n_fft={n_fft}"
+    if hop not in (n_fft // 8, n_fft // 4, n_fft // 2):
+        return f"the backward kernel needs hop_length in (n_fft/8, n_fft/4, n_fft/2), got hop_length={hop} for n_fft={n_fft}"
+    if n_mels > 256:
+        return f"the backward kernel takes n_mels <= 256, got {n_mels}"
+    if parts[0].shape[-1] <= n_fft // 2:
+        return f"T > n_fft/2 = {n_fft // 2} samples are needed (reflect padding), got T = {parts[0].shape[-1]}"
+    return None
+
+
+def melfeat_backward(x8, g_feats, feats, g_logmel, n_fft, hop, n_mels, tables, keep_workspace=False):
+    """`mst_melfeat_backward`: x8 (B, 8, T) fp32 CUDA contiguous, g_feats / feats (B, 64), g_logmel None or (B, 8, n_mels, F)
+    -> the stems' gradient (B, 8, T) of <g_feats, features> (+ <g_logmel, log-mel>, in the same adjoint pass).
+    keep_workspace: also return the workspace (its first B*8*n_mels*F floats hold the recomputed mel power)."""
+    B, _, T = x8.shape
+    win, band, bandw, width, melr = tables
+    L = _lib.lib()
+    need = L.mst_melfeat_backward_workspace_bytes(B, T, n_fft, hop, n_mels)
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=x8.device)
+    grad = torch.empty_like(x8)
+    g_feats, feats = g_feats.contiguous().float(), feats.contiguous().float()
+    if g_logmel is not None:
+        g_logmel = g_logmel.contiguous().float()
+    with torch.cuda.device(x8.device):
+        _lib.check(L.mst_melfeat_backward(_lib.dptr(x8), _lib.dptr(g_feats), _lib.dptr(feats), _lib.dptr(g_logmel), B, T, n_fft, hop,
+                                          n_mels, feats.shape[-1], _lib.dptr(win), _lib.dptr(band), _lib.dptr(bandw), width,
+                                          _lib.dptr(melr), _lib.dptr(grad), 0, _lib.dptr(ws), need, _lib.stream_ptr(x8.device)),
+                   "mst_melfeat_backward")
+    return (grad, ws) if keep_workspace else grad
+
+
+class _FeatGradHip(torch.autograd.Function):
+    """The mixing features with the gradient to the waveform.  Forward = the stage-A launch (bit-equal values to the no-grad
+    path).  Backward = `mst_melfeat_backward` (csrc/mrstft.hip): recomputes everything from the stems; bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, ext, vocals, bass, drums, other):
+        stems = (vocals, bass, drums, other)
+        _, feats = ext.plan().forward_stems({s: q.detach() for s, q in zip(STEMS, stems)}, False, True)
+        ctx.ext, ctx.shape = ext, vocals.shape
+        ctx.save_for_backward(feats, *stems)
+        return feats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        feats, *stems = ctx.saved_tensors
+        ext = ctx.ext
+        B, T = feats.shape[0], stems[0].shape[-1]
+        x = torch.cat([q.reshape(B, 2, T) for q in stems], dim=1)
+        grad = melfeat_backward(x, g, feats, None, ext.n_fft, ext.hop_length, ext.n_mels, ext._grad_tables(x.device))
+        return (None,) + tuple(grad[:, 2 * i:2 * i + 2].reshape(ctx.shape) if ctx.needs_input_grad[1 + i] else None
+                               for i in range(4))
+
+
 class LogMel:
     """A log-mel batch in one of the ENCODER-INTERNAL channel-minor layouts that stage A writes directly (include/mst.h
     MST_LOGMEL_CM32 / CM16): `data` (B, frames, n_mels, 8) fp32, or float16 high parts with the low parts in `lo`;
@@ -281,6 +368,11 @@ class MixingFeatureExtractor:
         self.use_detailed_spectral = use_detailed_spectral
         self.n_spectral_bins = n_spectral_bins
         self._plan = None
+        # gradient of the features to the stems: "none" (default) = the features carry no autograd history; "hip" = on CUDA fp32
+        # stems that require grad (grad mode on) `extract_all_features` returns features whose backward is
+        # `mst_melfeat_backward` -- what the kernel cannot take raises RuntimeError naming the reason, never a silent detach
+        self.grad_backend = "none"
+        self._grad_tabs = {}
         self.mel_transform = _MelTransformView(hann_window(n_fft), melscale_fbanks_htk(n_fft // 2 + 1, n_mels,
                                                                                       sample_rate))
 
@@ -308,11 +400,31 @@ class MixingFeatureExtractor:
 
     def extract_all_features(self, stems_dict):
         """stems_dict {stem: (2,T)} -> (feature_dim,)  [reference]; {stem: (B,2,T)} -> (B, feature_dim).
-        The features carry no autograd history, also when a stem does: they condition the encoder as constants (the reference
-        comments "no grad for feature extractor" at train_style_transfer.py:205)."""
+        With `grad_backend = "none"` (default) the features carry no autograd history, also when a stem does; with "hip" they
+        carry the reference's gradient to the stems (24 of the 64 basic features are live there)."""
         batched = next(iter(stems_dict.values())).dim() == 3
+        if self.grad_backend not in ("none", "hip"):
+            raise ValueError("grad_backend must be 'none' (default) or 'hip'")
+        if self.grad_backend == "hip" and torch.is_grad_enabled() and \
+                any(torch.is_tensor(q) and q.requires_grad for q in stems_dict.values()):
+            why = feature_grad_refusal(stems_dict, self.n_fft, self.hop_length, self.n_mels, self.use_detailed_spectral)
+            if why is None:
+                try:
+                    self._grad_tables(stems_dict[STEMS[0]].device)
+                except ValueError as e:
+                    why = str(e)
+            if why:
+                raise RuntimeError("MixingFeatureExtractor.grad_backend='hip': no gradient to the waveform for this call: " + why)
+            f = _FeatGradHip.apply(self, *[stems_dict[s] for s in STEMS])
+            return f if batched else f[0]
         _, f = self.plan().forward_stems(stems_dict, False, True)
         return f if batched else f[0]
+
+    def _grad_tables(self, device):
+        key = str(device)
+        if key not in self._grad_tabs:
+            self._grad_tabs[key] = grad_tables(self.plan().window, self.plan().fb, self.n_mels, device)
+        return self._grad_tabs[key]
 
     # ---- per-group views of the fused feature vector (reference public sub-methods)
     def _single(self, audio):

@@ -18,7 +18,9 @@ Forward paths
     eval mode, every parameter frozen -- trunk and head in libmst.so too (`_HipFrozenTrunk`: eval-mode forward that keeps the raw
     conv outputs, backward = pool / ReLU / affine pass, conv2 and conv1 input gradients; `_HipHead`).  With the default
     `input_grad_backend = "none"`, `encoder_backend = "hip"` raises for such a call.  The mixing features of the same launch
-    are constants.
+    are constants by default; `feature_grad_backend = "hip"` differentiates them too, as the reference does (stage A:
+    `mst_melfeat_backward`, fused with the log-mel backward; frozen trunk: `mst_encoder_frozen_film_grad`; FiLM MLP:
+    `mst_film_input_grad`).
 """
 import ctypes as C
 
@@ -31,7 +33,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from .mixing_utils import (LOGMEL_BAND_MAX, STEMS, LogMel, MelFeatPlan, detailed_bins_for_feature_dim, hann_window, is_deferred,
-                           mel_band_table, mel_bin_ranges, melscale_fbanks_htk, stems_to_tensor)
+                           feature_grad_refusal, mel_band_table, mel_bin_ranges, melfeat_backward, melscale_fbanks_htk,
+                           stems_to_tensor)
 
 
 class _Buf(nn.Module):
@@ -54,26 +57,42 @@ class _LogMelHip(torch.autograd.Function):
     """Stage A with the gradient to the waveform.  Forward = the stage-A launch in the reference layout (the same launch as
     the no-grad path: bit-equal values; the mixing features it can emit next to the log-mel are returned as constants).
     Backward = `mst_logmel_backward` (csrc/mrstft.hip): recomputes the frames and their mel power (only the stems are saved)
-    and runs the adjoint STFT with a fixed summation order (bit-reproducible)."""
+    and runs the adjoint STFT with a fixed summation order (bit-reproducible).
+    feat_grad (MixingStyleEncoder.feature_grad_backend = "hip"): the features are differentiable too; their cotangent and the
+    log-mel's go through ONE adjoint pass (`mst_melfeat_backward`)."""
 
     @staticmethod
-    def forward(ctx, pre, plan, want_feats, vocals, bass, drums, other):
+    def forward(ctx, pre, plan, want_feats, feat_grad, vocals, bass, drums, other):
         stems = (vocals, bass, drums, other)
         lm, feats = plan.forward_stems({s: q.detach() for s, q in zip(STEMS, stems)}, True, want_feats)
-        ctx.pre, ctx.shape = pre, vocals.shape
-        ctx.save_for_backward(*stems)
+        ctx.pre, ctx.shape, ctx.feat_grad = pre, vocals.shape, bool(feat_grad and feats is not None)
         if feats is None:
             feats = lm.new_empty(0)
-        ctx.mark_non_differentiable(feats)
+        if ctx.feat_grad:
+            ctx.set_materialize_grads(False)   # a cotangent that does not arrive costs nothing
+            ctx.save_for_backward(*stems, feats)
+        else:
+            ctx.save_for_backward(*stems)
+            ctx.mark_non_differentiable(feats)
         return lm, feats
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, g, _g_feats):
-        stems = ctx.saved_tensors
+    def backward(ctx, g, g_feats):
+        stems = ctx.saved_tensors[:4]
         pre = ctx.pre
-        B, _, M, Fr = g.shape
         T = stems[0].shape[-1]
+        if ctx.feat_grad:
+            feats = ctx.saved_tensors[4]
+            B = feats.shape[0]
+            if g is None and g_feats is None:
+                return (None,) * 8
+            x = torch.cat([q.reshape(B, 2, T) for q in stems], dim=1)
+            if g_feats is not None:
+                grad = melfeat_backward(x, g_feats, feats, g, pre.n_fft, pre.hop_length, pre.n_mels, pre._grad_tables(x.device))
+                return (None,) * 4 + tuple(grad[:, 2 * i:2 * i + 2].reshape(ctx.shape) if ctx.needs_input_grad[4 + i] else None
+                                           for i in range(4))
+        B, _, M, Fr = g.shape
         x = torch.cat([q.reshape(B, 2, T) for q in stems], dim=1)   # (B, 8, T), the row order of the log-mel
         g = g.contiguous().float()
         grad = torch.empty_like(x)
@@ -85,8 +104,8 @@ class _LogMelHip(torch.autograd.Function):
             _lib.check(L.mst_logmel_backward(_lib.dptr(x), _lib.dptr(g), B * 8, T, pre.n_fft, pre.hop_length, M, _lib.dptr(win),
                                              _lib.dptr(band), _lib.dptr(bandw), width, _lib.dptr(melr), _lib.dptr(grad), 0,
                                              _lib.dptr(ws), need, _lib.stream_ptr(x.device)), "mst_logmel_backward")
-        return (None, None, None) + tuple(grad[:, 2 * i:2 * i + 2].reshape(ctx.shape) if ctx.needs_input_grad[3 + i] else None
-                                          for i in range(4))
+        return (None,) * 4 + tuple(grad[:, 2 * i:2 * i + 2].reshape(ctx.shape) if ctx.needs_input_grad[4 + i] else None
+                                   for i in range(4))
 
 
 class MelSpectrogramPreprocessor(nn.Module):
@@ -145,8 +164,9 @@ class MelSpectrogramPreprocessor(nn.Module):
                                     melr.to(device))
         return self._grad_tabs[key]
 
-    def forward_with_grad(self, stems_dict, plan=None, want_feats=False):
-        """(log-mel with the gradient to the stems, mixing features of the same launch as constants or None)."""
+    def forward_with_grad(self, stems_dict, plan=None, want_feats=False, feat_grad=False):
+        """(log-mel with the gradient to the stems, mixing features of the same launch or None: constants, or with feat_grad
+        differentiable too -- basic 64-feature layout only)."""
         why = self._grad_refusal(stems_dict)
         if why is None:
             try:   # built here, not in backward: a filterbank the kernel cannot walk is refused before any launch
@@ -155,7 +175,8 @@ class MelSpectrogramPreprocessor(nn.Module):
                 why = str(e)
         if why:
             raise RuntimeError("MelSpectrogramPreprocessor: no gradient to the waveform for this call: " + why)
-        lm, feats = _LogMelHip.apply(self, plan or self.plan(), bool(want_feats), *[stems_dict[s] for s in STEMS])
+        lm, feats = _LogMelHip.apply(self, plan or self.plan(), bool(want_feats), bool(feat_grad and want_feats),
+                                     *[stems_dict[s] for s in STEMS])
         return lm, (feats if want_feats else None)
 
     def plan(self, detailed_bins=0) -> MelFeatPlan:
@@ -581,6 +602,26 @@ class HipEncoder:
                        "mst_encoder_frozen_backward_apply")
         return dy
 
+    def frozen_film_grad(self, layer, dpool, dfilm, B, frames, ws):
+        """The gradient to the FiLM tensor of conv layer 1 / 2 of the frozen trunk from the gradient of its pooled activation
+        (`mst_encoder_frozen_film_grad`): writes the layer's slots of dfilm (B, n_sub * 192) -- per band gamma1(32) beta1(32)
+        gamma2(64) beta2(64) -- and leaves the other layer's alone.  dpool, ws: as `frozen_backward_apply`."""
+        L = _lib.lib()
+        dev = dpool.device
+        dpool = dpool.contiguous().float()
+        W1 = frames // 5
+        if layer == 1:
+            st = (dpool.stride(0), dpool.stride(1), dpool.stride(2))
+        else:
+            W2 = W1 // 4
+            st = (dpool.shape[1] * W2, 64 * self.freq_dim * W2, self.freq_dim * W2)
+        assert dfilm.is_contiguous() and dfilm.dtype == torch.float32 and tuple(dfilm.shape) == (B, self.n_sub * 192)
+        with torch.cuda.device(dev):
+            _lib.check(L.mst_encoder_frozen_film_grad(self._h, layer, B, frames, _lib.dptr(dpool), st[0], st[1], st[2],
+                                                      _lib.dptr(dfilm), _lib.dptr(ws), ws.numel(), _lib.stream_ptr(dev)),
+                       "mst_encoder_frozen_film_grad")
+        return dfilm
+
     def conv1_dgrad(self, dy1, B, frames, ws=None):
         """gradient of the log-mel (B, 8, n_mels, frames) from dy1 (n_sub, B, 32, split_size, frames): per band the 7x7
         convolution with the transposed, flipped conv1 weights, then the bands added in ascending order
@@ -852,18 +893,28 @@ class _HipFrozenTrunk(torch.autograd.Function):
     last_timing = None
 
     @staticmethod
-    def forward(ctx, enc, logmel, feats):
+    def forward(ctx, enc, logmel, feats, film_w=None):
+        """film_w: the FiLM MLP's six tensors (mlp0 / mlp3 / film_head weight, bias) when `feats` may need a gradient
+        (feature_grad_backend = "hip"): backward then adds `frozen_film_grad` per layer and `mst_film_input_grad`."""
         B, _, M, Fr = logmel.shape
         _, t, ws = enc.forward_frozen(logmel, feats, head=False)
         ctx.enc, ctx.dims = enc, (B, Fr)
-        ctx.save_for_backward(ws)
+        if film_w is not None:
+            f = feats.detach().contiguous().float()
+            ctx.n_film = len(film_w)
+            ctx.save_for_backward(ws, f, *[q.detach().contiguous().float() for q in film_w])
+        else:
+            ctx.n_film = 0
+            ctx.save_for_backward(ws)
         return t["pool_in"]
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dpool_in):
         enc, (B, Fr) = ctx.enc, ctx.dims
-        ws, = ctx.saved_tensors
+        ws = ctx.saved_tensors[0]
+        want_feats = ctx.n_film > 0 and ctx.needs_input_grad[2]
+        dfilm = torch.empty(B, enc.n_sub * 192, device=dpool_in.device) if want_feats else None
         marks = []
 
         def mark(name):   # MST_TRAIN_TIMING=1: per-section GPU times of the last backward in _HipFrozenTrunk.last_timing
@@ -874,16 +925,43 @@ class _HipFrozenTrunk(torch.autograd.Function):
         mark("start")
         dy2 = enc.frozen_backward_apply(2, dpool_in, B, Fr, ws)
         mark("apply_bwd2")
-        dp1 = enc.conv2_dgrad(dy2, B, Fr)
-        mark("conv2_dgrad")
-        dy1 = enc.frozen_backward_apply(1, dp1, B, Fr, ws)
-        mark("apply_bwd1")
-        dlm = enc.conv1_dgrad(dy1, B, Fr, ws)
-        mark("conv1_dgrad")
+        if want_feats:
+            enc.frozen_film_grad(2, dpool_in, dfilm, B, Fr, ws)
+            mark("film_grad2")
+        dlm = dfeats = None
+        if ctx.needs_input_grad[1] or want_feats:
+            dp1 = enc.conv2_dgrad(dy2, B, Fr)
+            mark("conv2_dgrad")
+            if want_feats:
+                enc.frozen_film_grad(1, dp1, dfilm, B, Fr, ws)
+                mark("film_grad1")
+            if ctx.needs_input_grad[1]:
+                dy1 = enc.frozen_backward_apply(1, dp1, B, Fr, ws)
+                mark("apply_bwd1")
+                dlm = enc.conv1_dgrad(dy1, B, Fr, ws)
+                mark("conv1_dgrad")
+        if want_feats:
+            dfeats = _film_input_grad(ctx.saved_tensors[1], dfilm, ctx.saved_tensors[2:])
+            mark("film_input_grad")
         if _TRAIN_TIMING:
             torch.cuda.synchronize()
             _HipFrozenTrunk.last_timing = {b[0]: round(a[1].elapsed_time(b[1]), 3) for a, b in zip(marks[:-1], marks[1:])}
-        return None, dlm, None
+        return None, dlm, dfeats, None
+
+
+def _film_input_grad(feats, dfilm, film_w):
+    """`mst_film_input_grad`: d film (B, O) -> d feats (B, Fd) through the eval-mode FiLM MLP (weights: mlp0, mlp3, film_head)."""
+    B = feats.shape[0]
+    dims = _lib.FilmDims(film_w[0].shape[1], film_w[0].shape[0], film_w[4].shape[0])
+    L = _lib.lib()
+    work = torch.empty(L.mst_film_input_grad_workspace_bytes(C.byref(dims), B), dtype=torch.uint8, device=feats.device)
+    out = torch.empty_like(feats)
+    wp = _lib.FilmPtrs(*[t.data_ptr() for t in film_w])
+    with torch.cuda.device(feats.device):
+        _lib.check(L.mst_film_input_grad(C.byref(dims), C.byref(wp), _lib.dptr(feats), B, _lib.dptr(dfilm.contiguous().float()),
+                                         _lib.dptr(out), _lib.dptr(work), work.numel(), _lib.stream_ptr(feats.device)),
+                   "mst_film_input_grad")
+    return out
 
 
 def _seed64():
@@ -1039,6 +1117,15 @@ class MixingStyleEncoder(nn.Module):
         # encoder_backend == "hip" and the module is in eval mode with every parameter frozen -- a call this path cannot take
         # raises RuntimeError naming the reason
         self.input_grad_backend = "none"
+        # gradient through the MIXING FEATURES (the reference extracts the features of the mixer's output with gradients, so the
+        # waveform reaches the embedding a second time: features -> FiLM MLP -> gamma / beta of both conv layers): "none"
+        # (default) = the features are constants, and features that require grad are refused on the frozen HIP path; "hip" =
+        # in `forward(stems, features)` with a stem that requires grad, the features of the same stage-A launch that fill the
+        # deferred rows are differentiable (`mst_melfeat_backward`, fused with the log-mel backward), and features that carry
+        # history keep it: into the nn.Module FiLM MLP with encoder_backend = "torch", through `_HipFrozenTrunk`
+        # (`mst_encoder_frozen_film_grad`, `mst_film_input_grad`) with encoder_backend = "hip" + input_grad_backend = "hip".
+        # Eval mode, basic 64-feature layout; anything else raises RuntimeError naming the reason.
+        self.feature_grad_backend = "none"
         # precision of the hand-written training trunk: "fp32" (exact), "f16" (float16 operands, fp32 accumulation:
         # the reference's --use_amp arithmetic, see include/mst.h mst_encoder_set_train_precision), "f16x3" (the same
         # kernels with 3-term split-precision operands: fp32-equivalent), or "auto" = f16 inside `torch.autocast(dtype=float16)`
@@ -1252,8 +1339,12 @@ class MixingStyleEncoder(nn.Module):
         if live:
             return (f"{len(live)} encoder parameters require grad (first: {live[0]}); this path differentiates the input only: "
                     "freeze them with requires_grad_(False)")
-        if mixing_features.requires_grad:
-            return "mixing_features requires grad; the mixing features are constants on this path: detach them"
+        feat_grad = self.feature_grad_backend == "hip"
+        if mixing_features.requires_grad and not feat_grad:
+            return ("mixing_features requires grad; the mixing features are constants on this path: detach them "
+                    "(feature_grad_backend=\"hip\" differentiates them)")
+        if feat_grad:
+            mixing_features = mixing_features.detach()   # (the limits below are about sizes and dtypes)
         if not on_gpu or not (mixing_features.is_cuda or features_follow):
             return "non-CUDA tensors: libmst kernels need CUDA (HIP) tensors and there is no CPU fallback"
         if dtype != torch.float32 or mixing_features.dtype != torch.float32 or self.film_encoder.film_head.weight.dtype != torch.float32:
@@ -1279,8 +1370,12 @@ class MixingStyleEncoder(nn.Module):
     def _forward_frozen_hip(self, logmel, mixing_features):
         """Frozen encoder with the gradient to the log-mel: trunk (_HipFrozenTrunk) and head (_HipHead, no Dropout) in libmst.so."""
         self._require_frozen_path(logmel.shape[-1], logmel.is_cuda, logmel.dtype, mixing_features)
-        ap = self.audio_encoder.attention_pooling
-        pool_in = _HipFrozenTrunk.apply(self.hip_encoder(), logmel, mixing_features)
+        ap, fe = self.audio_encoder.attention_pooling, self.film_encoder
+        film_w = None
+        if self.feature_grad_backend == "hip" and mixing_features.requires_grad:
+            film_w = (fe.feature_mlp[0].weight, fe.feature_mlp[0].bias, fe.feature_mlp[3].weight, fe.feature_mlp[3].bias,
+                      fe.film_head.weight, fe.film_head.bias)
+        pool_in = _HipFrozenTrunk.apply(self.hip_encoder(), logmel, mixing_features, film_w)
         return _HipHead.apply(pool_in, 0.0, 0.0, ap.attention[0].weight, ap.attention[0].bias, ap.attention[2].weight,
                               ap.attention[2].bias, ap.projection[0].weight, ap.projection[0].bias)
 
@@ -1289,10 +1384,18 @@ class MixingStyleEncoder(nn.Module):
             raise ValueError("train_backend must be 'hip' (default; alias 'hip-strict'), 'torch' or 'hip-or-torch'")
         if self.input_grad_backend not in ("none", "hip"):
             raise ValueError("input_grad_backend must be 'none' (default) or 'hip'")
+        if self.feature_grad_backend not in ("none", "hip"):
+            raise ValueError("feature_grad_backend must be 'none' (default) or 'hip'")
         auto = self._needs_autograd(mixing_features)
+        feat_grad = self.feature_grad_backend == "hip" and mixing_features.requires_grad
         if self.input_grad_backend == "hip" and self.encoder_backend == "hip" and torch.is_grad_enabled() and \
-                torch.is_tensor(logmel) and logmel.requires_grad and not (self.training and auto and self.train_backend == "torch"):
+                torch.is_tensor(logmel) and (logmel.requires_grad or feat_grad) and \
+                not (self.training and auto and self.train_backend == "torch"):
             return self._forward_frozen_hip(logmel, mixing_features)
+        if feat_grad and torch.is_grad_enabled() and not auto and self.encoder_backend == "hip":
+            raise RuntimeError("MixingStyleEncoder.feature_grad_backend='hip': mixing_features requires grad, but the hand-written HIP "
+                               "trunk (encoder_backend='hip') differentiates them only on the frozen path: set "
+                               "input_grad_backend=\"hip\" (eval mode, frozen parameters) or encoder_backend=\"torch\"")
         hip_train = self.encoder_backend == "hip" and self.training and auto and self.train_backend in self._HIP_TRAIN_BACKENDS
         if hip_train:   # decided BEFORE any layout conversion, so that a refusal names its reason
             why = self._hip_trunk_refusal(logmel)
@@ -1352,7 +1455,8 @@ class MixingStyleEncoder(nn.Module):
         if pre.wants_grad(stems_dict):
             # the style term of the style-transfer trainer (src/train_style_transfer.py:192-224): the gradient of the embedding to
             # the WAVEFORM.  Stage A forward and backward run in HIP (_LogMelHip); the conv trunk, FiLM and the head on
-            # PyTorch-ROCm autograd.  The mixing features of the same launch condition the encoder as constants.
+            # PyTorch-ROCm autograd.  The mixing features of the same launch condition the encoder as constants, unless
+            # feature_grad_backend = "hip" differentiates them too (below).
             # With input_grad_backend = "hip" (and encoder_backend = "hip", model.eval(), frozen parameters) the trunk and the
             # head run in libmst.so too (_HipFrozenTrunk, _HipHead): forward_from_logmel takes the log-mel that requires grad.
             if not (self.encoder_backend == "torch" or (self.training and auto and self.train_backend == "torch")):
@@ -1363,7 +1467,14 @@ class MixingStyleEncoder(nn.Module):
                                        "frozen encoder's input gradient in HIP as well (detach the stems if no waveform gradient is wanted)")
                 first = next(iter(stems_dict.values()))
                 self._require_frozen_path(1 + first.shape[-1] // pre.hop_length, first.is_cuda, first.dtype, mixing_features, True)
-            logmel, feats = pre.forward_with_grad(stems_dict, plan, has_feats)
+            feat_grad = self.feature_grad_backend == "hip"
+            if feat_grad:   # the features of this launch are differentiable too (the reference's second path to the embedding)
+                why = "the module is in training mode (train-mode FiLM gradients are not built): call model.eval()" if self.training \
+                    else feature_grad_refusal(stems_dict, pre.n_fft, pre.hop_length, pre.n_mels, bool(bins))
+                if why:
+                    raise RuntimeError("MixingStyleEncoder.feature_grad_backend='hip': no gradient through the mixing features for "
+                                       "this call: " + why)
+            logmel, feats = pre.forward_with_grad(stems_dict, plan, has_feats, feat_grad)
         else:
             with torch.no_grad():
                 logmel, feats = plan.forward_stems(stems_dict, True, has_feats, layout, want_absmax=layout == _lib.LOGMEL_CM16,
