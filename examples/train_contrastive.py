@@ -94,6 +94,8 @@ def main(argv=None):
     ap.add_argument("--discriminator-backend", choices=["hip", "torch"], default="hip",
                     help="discriminator and cosine loss: hand-written forward / backward (csrc/head.hip) or PyTorch ops")
     ap.add_argument("--checkpoint", type=str, default=None, help="write a checkpoint here after the last step")
+    ap.add_argument("--optimizer", choices=["torch", "hip"], default="torch",
+                    help="AdamW of torch.optim, or of mst_amd.optim (csrc/optim.hip: two launches per step, same state_dict keys)")
     a = ap.parse_args(argv)
     if a.use_adversarial and not a.song_id_cache_path:
         ap.error("--use_adversarial needs --song_id_cache_path")
@@ -123,13 +125,16 @@ def main(argv=None):
         grl_layer = GradientReversalLayer(init_lambda=0.0).to(dev)
         print(f"adversarial: {song_id_embeddings.shape[0]} song-identity embeddings of dimension {song_id_embeddings.shape[1]}, "
               f"{sum(q.numel() for q in discriminator.parameters()):,} discriminator parameters", flush=True)
+    AdamW = torch.optim.AdamW
+    if a.optimizer == "hip":
+        from mst_amd.optim import AdamW
     if a.use_adversarial and a.discriminator_lr is not None:
-        opt = torch.optim.AdamW(model.parameters(), lr=a.lr)
-        disc_opt = torch.optim.AdamW(discriminator.parameters(), lr=a.discriminator_lr)
+        opt = AdamW(model.parameters(), lr=a.lr)
+        disc_opt = AdamW(discriminator.parameters(), lr=a.discriminator_lr)
     elif a.use_adversarial:
-        opt = torch.optim.AdamW(list(model.parameters()) + list(discriminator.parameters()), lr=a.lr)
+        opt = AdamW(list(model.parameters()) + list(discriminator.parameters()), lr=a.lr)
     else:
-        opt = torch.optim.AdamW(model.parameters(), lr=a.lr)
+        opt = AdamW(model.parameters(), lr=a.lr)
     stager = ingest.DeviceStager((2 * a.batch_size, 8, ds.clip_samples), torch.int16, dev)
     losses, step = [], 0
     it = iter(dl)

@@ -15,7 +15,9 @@ embeddings for the two styles,
     cycle = tcn(out, film(target_emb, input_emb))
     loss  = MRSTFT(out, target) + lambda_cycle * MRSTFT(cycle, input)
 
-AdamW, and the reference's two clip_grad_norm_ calls.
+AdamW, and the reference's two clip_grad_norm_ calls: torch.optim / torch.nn.utils by default (`--optimizer torch`), or the
+kernels of csrc/optim.hip (`--optimizer hip`: `mst_amd.optim.AdamW` and `mst_amd.optim.clip_grad_norm_`, three launches per
+clip and two per step whatever the number of tensors, the clip's norm summed in double in a fixed order).
 
 `--style-weight W` (default 0: the loop above, unchanged) adds the reference's style term (:192-224),
 
@@ -76,6 +78,8 @@ def main(argv=None):
                          "(feature_grad_backend='hip': the second path from the waveform to the embedding)")
     ap.add_argument("--film-generator", choices=("torch", "hip"), default="torch",
                     help="the FiLM generator's training step: PyTorch-ROCm modules, or the hand-written HIP forward and backward")
+    ap.add_argument("--optimizer", choices=("torch", "hip"), default="torch",
+                    help="AdamW and the two clip_grad_norm_ calls: torch.optim / torch.nn.utils, or the hand-written HIP kernels")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("train_tcn_mixer.py needs a GPU (backend='hip-train' has no CPU fallback)")
@@ -87,7 +91,10 @@ def main(argv=None):
     if a.film_generator == "hip":
         gen.backend, gen.train_backend = "hip", "hip"
     mrstft = MultiResolutionSTFTLoss()
-    opt = torch.optim.AdamW(list(tcn.parameters()) + list(gen.parameters()), lr=a.lr)
+    AdamW, clip_grad_norm_ = torch.optim.AdamW, torch.nn.utils.clip_grad_norm_
+    if a.optimizer == "hip":
+        from mst_amd.optim import AdamW, clip_grad_norm_
+    opt = AdamW(list(tcn.parameters()) + list(gen.parameters()), lr=a.lr)
 
     x = synth_batch(a.batch_size, int(a.seconds * 44100)).to(dev)
     target = other_mix(x)
@@ -123,8 +130,8 @@ def main(argv=None):
             style = cosine_distance_loss(encoder(as_stems(out), feats), style_target)
             loss = loss + a.style_weight * style
         loss.backward()
-        torch.nn.utils.clip_grad_norm_(tcn.parameters(), max_norm=1.0)
-        torch.nn.utils.clip_grad_norm_(gen.parameters(), max_norm=1.0)
+        clip_grad_norm_(tcn.parameters(), max_norm=1.0)
+        clip_grad_norm_(gen.parameters(), max_norm=1.0)
         opt.step()
         extra = f", style {style.item():.6f}" if encoder is not None else ""
         print(f"step {step} loss {loss.item():.6f} (target {fit.item():.6f}, cycle {cycle.item():.6f}{extra})", flush=True)

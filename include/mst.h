@@ -737,6 +737,82 @@ int mst_tcn_film_backward(const mst_tcn_film_train_dims* dims, const mst_tcn_fil
                           const void* save, const mst_tcn_film_grads* grads, float* demb, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The optimiser tail: gradient clipping and the parameter update of both trainers and of the per-pair fit
+ * (clip_grad_norm_ + AdamW src/train_style_transfer.py:284-288, 602-605; AdamW under GradScaler src/train.py:292-296,
+ * 323-326; Adam / AdamW / SGD(momentum=0.9) of the fit inference/test_tcn_style_transfer.py:130-189, grid_search_tcn.py:92-97).
+ *
+ * Multi-tensor form: one call handles an ordered list of fp32 tensors, described by two DEVICE tables the caller builds once
+ * and keeps while a call is in flight (mst_optim_list holds their device pointers and is itself read on the host):
+ *   tensors   [n_tensors] mst_optim_tensor: parameter, gradient, state and step-count pointers and the element count n >= 1;
+ *   chunk_map [n_chunks][2] int32: (tensor index, chunk index inside that tensor), one row per chunk of
+ *             mst_optim_chunk_elems() elements, chunk c of a tensor covering elements [c * chunk, min(n, (c + 1) * chunk)).
+ *             One workgroup serves one row.  The rows of the map must cover every tensor exactly once (the library cannot
+ *             check device memory; a row past its tensor's end is ignored).
+ * Pointers need 4-byte alignment only (views at odd element offsets are fine): 16-byte accesses are used between a scalar
+ * head and tail where a tensor's arrays allow it.  An element's result depends on its own inputs and the call's scalars only,
+ * not on the list, its position or its chunk: every stored value is the double-precision evaluation of the formula on the fp32
+ * inputs, rounded once.  No float atomics, no workgroup waits on another; no allocation, no host synchronisation; capturable.
+ *
+ * mst_optim_grad_norm: *norm = fp32(sqrt(sum g^2)) over the whole list -- squares and sums in double, one partial per chunk
+ *   (workspace), the partials added in index order by a second launch -- and *coef = min(1, max_norm * (1 / (norm + 1e-6)))
+ *   evaluated in fp32, the arithmetic of torch.nn.utils.clip_grad_norm_ (its scalar / tensor is reciprocal-then-multiply).
+ *   A NaN norm gives a NaN coefficient; an infinite norm gives 0, as torch's does.  Reads tensors[i].grad and n only.
+ * mst_optim_scale_grads: g *= *coef, one fp32 multiply per element.
+ * mst_optim_step: one step of torch.optim's single-tensor formulas, per element
+ *   MST_OPTIM_ADAM   g += wd p;  m += (g - m)(1 - b1);  v = b2 v + (1 - b2) g g;  p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+ *   MST_OPTIM_ADAMW  p *= 1 - lr wd;  then as Adam without the first term
+ *   MST_OPTIM_SGD    g += wd p;  buf = momentum buf + g  (a zero buffer: the first step's copy of g);  p -= lr buf
+ *                    (momentum == 0: state1 may be NULL and p -= lr g)
+ *   state1 = exp_avg / momentum_buffer, state2 = exp_avg_sq (Adam, AdamW), step = dev fp32 scalar per tensor (Adam, AdamW):
+ *   the call first adds 1 to it, t is the new value, and the bias corrections are formed from it on the device in double.
+ *   Hyper-parameters are passed by value (a host struct read during the call).  amsgrad, maximize, nesterov and
+ *   dampening != 0 are refused by name.
+ *   grad_scale (dev fp32 scalar or NULL): the gradient is multiplied by 1 / *grad_scale before use (the stored gradient is
+ *   left as it is).  found_inf (dev fp32 scalar or NULL): when non-zero the call changes nothing -- parameters, state and
+ *   step counts keep their bits (the contract of PyTorch's fused optimisers under GradScaler).
+ *   Workspace (Adam, AdamW; SGD takes NULL): mst_optim_step_workspace_bytes(n_tensors).
+ * mst_keep_best: the fit loop's best-so-far bookkeeping without a host read.  With dev scalars *loss and *best:
+ *   history[index] = *loss (unless history is NULL); if *loss < *best (strictly: the first minimum wins, a NaN never does):
+ *   every copies[k].src is copied to its dst (bytes and pointers multiples of 4, at most 8 copies, src and dst disjoint),
+ *   *best = *loss and *best_index = index.  `copies` is a host array read during the call.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct mst_optim_tensor {
+  float* param;
+  float* grad;
+  float* state1;
+  float* state2;
+  float* step;
+  long long n;
+} mst_optim_tensor;
+typedef struct mst_optim_list {
+  const mst_optim_tensor* tensors; /* dev [n_tensors]   */
+  const int32_t* chunk_map;        /* dev [n_chunks][2] */
+  int32_t n_tensors, n_chunks;
+} mst_optim_list;
+#define MST_OPTIM_ADAM 0
+#define MST_OPTIM_ADAMW 1
+#define MST_OPTIM_SGD 2
+typedef struct mst_optim_hyper {
+  int32_t algo, amsgrad, maximize, nesterov;
+  double lr, beta1, beta2, eps, weight_decay, momentum, dampening;
+} mst_optim_hyper;
+typedef struct mst_keep_copy {
+  const void* src;
+  void* dst;
+  long long bytes;
+} mst_keep_copy;
+int mst_optim_chunk_elems(void);
+size_t mst_optim_grad_norm_workspace_bytes(int n_chunks);
+int mst_optim_grad_norm(const mst_optim_list* list, float max_norm, float* norm, float* coef, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int mst_optim_scale_grads(const mst_optim_list* list, const float* coef, void* stream);
+size_t mst_optim_step_workspace_bytes(int n_tensors);
+int mst_optim_step(const mst_optim_list* list, const mst_optim_hyper* hyper, const float* grad_scale, const float* found_inf,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int mst_keep_best(const float* loss, float* best, int32_t* best_index, float* history, int index, const mst_keep_copy* copies,
+                  int n_copies, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

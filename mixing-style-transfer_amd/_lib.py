@@ -124,6 +124,22 @@ class TcnFilmGrads(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("mlp0_w", "mlp0_b", "mlp3_w", "mlp3_b", "mlp6_w", "mlp6_b")]
 
 
+class OptimList(C.Structure):   # mst_optim_list; the rows of `tensors` are 6 x 8 bytes (mst_optim_tensor)
+    _fields_ = [("tensors", C.c_void_p), ("chunk_map", C.c_void_p), ("n_tensors", C.c_int32), ("n_chunks", C.c_int32)]
+
+
+OPTIM_ADAM, OPTIM_ADAMW, OPTIM_SGD = 0, 1, 2
+
+
+class OptimHyper(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("algo", "amsgrad", "maximize", "nesterov")] + \
+               [(k, C.c_double) for k in ("lr", "beta1", "beta2", "eps", "weight_decay", "momentum", "dampening")]
+
+
+class KeepCopy(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("bytes", C.c_longlong)]
+
+
 SYMBOLS = {
     "mst_version": (C.c_int, []),
     "mst_last_error": (C.c_char_p, []),
@@ -268,6 +284,14 @@ SYMBOLS = {
     "mst_tcn_film_backward": (C.c_int, [C.POINTER(TcnFilmTrainDims), C.POINTER(TcnFilmWeights), C.c_void_p, C.c_int, C.c_float,
                                         C.c_float, C.c_uint64, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p,
                                         C.POINTER(TcnFilmGrads), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mst_optim_chunk_elems": (C.c_int, []),
+    "mst_optim_grad_norm_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "mst_optim_grad_norm": (C.c_int, [C.POINTER(OptimList), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mst_optim_scale_grads": (C.c_int, [C.POINTER(OptimList), C.c_void_p, C.c_void_p]),
+    "mst_optim_step_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "mst_optim_step": (C.c_int, [C.POINTER(OptimList), C.POINTER(OptimHyper), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                 C.c_void_p]),
+    "mst_keep_best": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(KeepCopy), C.c_int, C.c_void_p]),
 }
 
 _lib = None

@@ -19,6 +19,9 @@ Same class names, constructor arguments, defaults and `state_dict` keys as the r
     or one that needs a gradient runs `mst_tcn_film_forward_train` / `mst_tcn_film_backward` (csrc/head.hip) as an autograd
     function on the module's live parameters: Dropout from seeds of torch's CPU generator, all six parameter gradients and,
     when the embedding requires one, its gradient.  `eval()` without gradients stays on the inference handle.
+
+`optimize_tcn_style_transfer` is the reference's per-pair fit (inference/test_tcn_style_transfer.py:84-201) on these backends and
+`mst_amd.optim`, without a host synchronisation inside its loop.
 """
 import ctypes as C
 import math
@@ -657,3 +660,109 @@ def apply_style_transfer(tcn, film_generator, stems_input, target_embedding, inp
         out = {s: y[0, 2 * i:2 * i + 2, :].cpu() for i, s in enumerate(STEM_ORDER)}
         mixture = sum(out.values())
     return {"processed_stems": out, "processed_mixture": mixture}
+
+
+_FIT_OPTIMIZERS = ("adam", "adamw", "sgd")
+
+
+def _fit_refusal(tcn, mixing_model, optimizer, sync):
+    """Why `optimize_tcn_style_transfer` cannot run with these objects (None = it can); decided before anything touches a GPU."""
+    if optimizer not in _FIT_OPTIMIZERS:
+        return f"optimizer={optimizer!r}: 'adam' (default), 'adamw' or 'sgd'"
+    if sync not in ("deferred", "step"):
+        return f"sync={sync!r}: 'deferred' (default: no host synchronisation inside the loop) or 'step'"
+    if mixing_model.training:
+        return ("mixing_model is in train() mode; the fit differentiates the stems through a FROZEN encoder (eval-mode BatchNorm, "
+                "no Dropout): call mixing_model.eval()")
+    live = [n for n, q in mixing_model.named_parameters() if q.requires_grad]
+    if live:
+        return (f"{len(live)} parameters of mixing_model require grad (first: {live[0]}); the fit optimises the TCN alone: freeze "
+                f"them with requires_grad_(False)")
+    if getattr(mixing_model, "encoder_backend", None) != "hip" or getattr(mixing_model, "input_grad_backend", None) != "hip":
+        return ("mixing_model must run its input gradient on the HIP kernels: encoder_backend='hip' with input_grad_backend='hip' "
+                f"(got {getattr(mixing_model, 'encoder_backend', None)!r}, {getattr(mixing_model, 'input_grad_backend', None)!r})")
+    if tcn.use_film:
+        return "the fit optimises a mixer without FiLM (use_film=False), as the reference's does"
+    return None
+
+
+def optimize_tcn_style_transfer(tcn, stems_input, target_emb, mixing_model, feature_extractor, device, num_steps=200, lr=0.01,
+                                verbose=True, *, optimizer="adam", sync="deferred"):
+    """The reference's per-pair fit (inference/test_tcn_style_transfer.py:84-201; its optimiser choices grid_search_tcn.py:92-97):
+    `num_steps` steps that move the TCN's parameters so that the embedding of the processed stems approaches `target_emb`, every
+    step on the HIP kernels -- train-mode TCN forward and backward (`backend = "hip-train"`), the frozen `mixing_model`'s input
+    gradient (it must be in eval() with every parameter frozen, `encoder_backend="hip"`, `input_grad_backend="hip"`;
+    `feature_grad_backend` as the caller set it), `cosine_distance_loss` against the normalised target, and the step of
+    `mst_amd.optim.Adam` / `AdamW` / `SGD(momentum=0.9)`.  The mixing features come from the deferred placeholder, i.e. from the
+    encoder's own stage-A launch; `feature_extractor` is accepted for the reference's signature and not read.
+
+    `sync="deferred"` makes no host synchronisation inside the loop: the distance history and the best output are kept on the
+    device by `mst_keep_best` and read back once after the last step (`verbose` prints from the history then).  `sync="step"`
+    reads the distance every step and tracks the best on the host, with the reference's live progress lines: the same kernels,
+    so the same bits.  As in the reference, the output of step k is produced BEFORE update k, the first minimum wins, and
+    `converged = best < 0.8 * distances[0]`.  The mixture is the sum of the best step's stems, formed once at the end.  The
+    reference's `tcn_state` key (a shallow copy that aliases the live parameters; nobody reads it) is not reproduced, nor is its
+    verbose-only extra forward before the loop.
+
+    Returns {"processed_stems": {stem: (2, T) cpu}, "processed_mixture": (2, T) cpu, "distances": [float] * num_steps,
+    "final_distance": float, "converged": bool}."""
+    from . import optim as hip_optim
+    from .loss import cosine_distance_loss
+    from .mixing_utils import deferred_features
+    why = _fit_refusal(tcn, mixing_model, optimizer, sync)
+    if why:
+        raise RuntimeError("optimize_tcn_style_transfer: " + why)
+    if num_steps < 1:
+        raise ValueError(f"num_steps must be at least 1, got {num_steps}")
+    device = torch.device(device)
+    target = F.normalize(target_emb.detach().to(device, torch.float32), p=2, dim=0).unsqueeze(0)
+    x = torch.cat([stems_input[s] for s in STEM_ORDER], dim=0).unsqueeze(0).to(device).contiguous()   # (1, 8, T)
+    tcn = tcn.to(device)
+    tcn.backend = "hip-train"
+    tcn.train()
+    params = list(tcn.parameters())
+    opt = {"adam": lambda: hip_optim.Adam(params, lr=lr), "adamw": lambda: hip_optim.AdamW(params, lr=lr),
+           "sgd": lambda: hip_optim.SGD(params, lr=lr, momentum=0.9)}[optimizer]()
+    feats = deferred_features(mixing_model.film_encoder.feature_dim).unsqueeze(0).to(device)
+    deferred = sync == "deferred"
+    if deferred:
+        best = torch.full((), float("inf"), dtype=torch.float32, device=device)
+        best_index = torch.full((), -1, dtype=torch.int32, device=device)
+        history = torch.zeros(num_steps, dtype=torch.float32, device=device)
+        best_y = torch.zeros_like(x)
+    else:
+        distances, best_distance, best_y = [], float("inf"), None
+
+    def progress(step, distance, best_so_far):
+        if verbose and (step % 10 == 0 or step == num_steps - 1):
+            print(f"Step {step:3d}/{num_steps}: distance = {distance:.4f}, loss = {distance:.4f}, best = {best_so_far:.4f}")
+
+    for step in range(num_steps):
+        opt.zero_grad()
+        y = tcn(x)
+        emb = mixing_model({s: y[:, 2 * i:2 * i + 2] for i, s in enumerate(STEM_ORDER)}, feats)
+        loss = cosine_distance_loss(emb, target)
+        if deferred:
+            hip_optim.keep_best(loss.detach(), best, best_index, history, step, [(y.detach(), best_y)])
+        else:
+            distance = loss.item()
+            distances.append(distance)
+            if distance < best_distance:
+                best_distance, best_y = distance, y.detach().cpu()
+        loss.backward()
+        opt.step()
+        if not deferred:
+            progress(step, distance, best_distance)
+    if deferred:
+        distances = history.cpu().tolist()   # the one read-back
+        best_distance, best_y = float(best.cpu()), best_y.cpu()
+        running = float("inf")
+        for step, d in enumerate(distances):
+            running = d if d < running else running
+            progress(step, d, running)
+    if best_distance == float("inf"):
+        raise RuntimeError("optimize_tcn_style_transfer: no step produced a distance below infinity (NaN in the stems, the target "
+                           "or the encoder?)")
+    stems = {s: best_y[0, 2 * i:2 * i + 2] for i, s in enumerate(STEM_ORDER)}
+    return {"processed_stems": stems, "processed_mixture": sum(stems.values()), "distances": distances,
+            "final_distance": best_distance, "converged": best_distance < distances[0] * 0.8}
