@@ -6,7 +6,8 @@
 //       h1 = Dropout(ReLU(W1 f + b1));  h2 = ReLU(W3 h1 + b3);  film = Wh h2 + bh
 //   * (at the end of the file) the song-identity discriminator and the cosine-distance loss of the adversarial branch, and the
 //     FiLM generator of the TCN mixer (reference src/tcn_mixer.py:148-216) in training
-// with the gradients autograd derives from them.  fp32 throughout (products on v_mfma_f32_16x16x4_f32 where a GEMM is large
+// with the gradients autograd derives from them.  fp32 (the head's scores, softmax, softmax backward and sums over frames, and the
+// slice sums of the FiLM MLP's d h2, in double: the cancelling paths; products on v_mfma_f32_16x16x4_f32 where a GEMM is large
 // enough to matter, fp32 FMA chains elsewhere); every reduction has a fixed order (no atomics): bit-deterministic.
 // Dropout masks are never stored: a keep decision is a pure function of (seed, element index) (Philox-2x32-10, common.h) and
 // every kernel that touches a dropped tensor re-derives it.
@@ -105,13 +106,20 @@ __global__ __launch_bounds__(256) void gemm_kernel(int M, int N, int K, int Z, i
     }
 }
 // sum of the S slices' partial results [S][count] in slice order, handed to the epilogue functor element by element
-template <class FE>
+// (WIDE: the slices are added in double and rounded once -- for the products cut into many short slices)
+template <bool WIDE, class FE>
 __global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restrict__ part, int S, long long count, FE fe) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= count) return;
-  float s = 0.f;
-  for (int k = 0; k < S; ++k) s += part[(size_t)k * count + i];
-  fe(i, s);
+  if (WIDE) {
+    double s = 0.0;
+    for (int k = 0; k < S; ++k) s += (double)part[(size_t)k * count + i];
+    fe(i, (float)s);
+  } else {
+    float s = 0.f;
+    for (int k = 0; k < S; ++k) s += part[(size_t)k * count + i];
+    fe(i, s);
+  }
 }
 struct PartEpi {   // partial sums of slice s -> part[s][m][n]
   float* part; int M, N;
@@ -164,6 +172,21 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ A
 // ------------------------------------------------------------------------------------------
 // attention pooling
 // ------------------------------------------------------------------------------------------
+// The scores, the softmax over frames and its backward are formed in double (a few thousand values per clip): the gradients of
+// attention.0 / attention.2 are sums over frames of ds_t = a_t (da_t - sum a da) times a bounded factor, sum_t ds_t = 0, so a
+// relative error of 2^-24 in the weights a_t or in the difference survives the cancellation at full size.  With fp32 here the
+// attention.0.bias gradient is as far from float64 as any fp32 evaluation (1e-4 of its maximum element-wise); with double it is
+// 3 to 10 times closer.
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_max_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
 // xd = Dropout(x), materialised once per forward pass (the GEMM operand loaders would otherwise spend more time on the keep
 // decisions than the matrix cores on the products)
 __global__ __launch_bounds__(256) void dropout_fwd_kernel(const float* __restrict__ x, float* __restrict__ xd, long long n, Drop d) {
@@ -178,35 +201,40 @@ __global__ __launch_bounds__(256) void dropout_fwd_kernel(const float* __restric
 __global__ __launch_bounds__(256) void head_pool_kernel(const float* __restrict__ x, const float* __restrict__ h, const float* __restrict__ w2,
                                                         const float* __restrict__ b2, float* __restrict__ a_out, float* __restrict__ pooled,
                                                         int C, int T, int A) {   // x = xd (already dropped)
-  extern __shared__ float sm[];   // [T] scores -> weights
-  __shared__ float red[8];
+  extern __shared__ double sd[];   // [T] scores -> exp (double), then [T] weights (float)
+  float* sm = reinterpret_cast<float*>(sd + T);
+  __shared__ double red[8];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int t = wave; t < T; t += 4) {   // a wave per frame: lanes over the hidden units
     const float* hr = h + ((size_t)b * T + t) * A;
-    float s = 0.f;
-    for (int j = lane; j < A; j += 64) s = fmaf(w2[j], hr[j], s);
-    s = mst::wave_sum(s);
-    if (lane == 0) sm[t] = s + b2[0];
+    double s = 0.0;
+    for (int j = lane; j < A; j += 64) s = fma((double)w2[j], (double)hr[j], s);
+    s = wave_sum_d(s);
+    if (lane == 0) sd[t] = s + (double)b2[0];
   }
   __syncthreads();
-  float mx = -INFINITY;
-  for (int t = tid; t < T; t += 256) mx = fmaxf(mx, sm[t]);
-  mx = mst::wave_max(mx);
+  double mx = -INFINITY;
+  for (int t = tid; t < T; t += 256) mx = fmax(mx, sd[t]);
+  mx = wave_max_d(mx);
   if (lane == 0) red[wave] = mx;
   __syncthreads();
-  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  float sum = 0.f;
+  mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+  double sum = 0.0;
   for (int t = tid; t < T; t += 256) {
-    const float e = expf(sm[t] - mx);
-    sm[t] = e;
+    const double e = exp(sd[t] - mx);
+    sd[t] = e;   // (only this thread touches frame t)
     sum += e;
   }
-  sum = mst::wave_sum(sum);
+  sum = wave_sum_d(sum);
   if (lane == 0) red[4 + wave] = sum;
   __syncthreads();
-  const float inv = 1.0f / ((red[4] + red[5]) + (red[6] + red[7]));
-  if (blockIdx.y == 0)
-    for (int t = tid; t < T; t += 256) a_out[(size_t)b * T + t] = sm[t] * inv;
+  const double invd = 1.0 / ((red[4] + red[5]) + (red[6] + red[7]));
+  for (int t = tid; t < T; t += 256) {
+    const float a = (float)(sd[t] * invd);
+    sm[t] = a;
+    if (blockIdx.y == 0) a_out[(size_t)b * T + t] = a;
+  }
+  __syncthreads();
   const int c_per_blk = (C + gridDim.y - 1) / gridDim.y;
   const int c0 = blockIdx.y * c_per_blk, c1 = min(C, c0 + c_per_blk);
   const float* xb = x + (size_t)b * C * T;
@@ -214,7 +242,7 @@ __global__ __launch_bounds__(256) void head_pool_kernel(const float* __restrict_
   for (int c = c0 + wave * 4 + sub; c < c1 + 3; c += 16) {   // 16 lanes per channel
     float v = 0.f;
     if (c < c1)
-      for (int t = l16; t < T; t += 16) v = fmaf(xb[(size_t)c * T + t], sm[t] * inv, v);
+      for (int t = l16; t < T; t += 16) v = fmaf(xb[(size_t)c * T + t], sm[t], v);
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     if (l16 == 0 && c < c1) pooled[(size_t)b * C + c] = v;
@@ -248,28 +276,28 @@ __global__ __launch_bounds__(256) void head_da_kernel(const float* __restrict__ 
 }
 // block per clip: da_t = sum of the slices (fixed order);  ds_t = a_t (da_t - sum_t' a_t' da_t')
 __global__ __launch_bounds__(256) void head_ds_kernel(const float* __restrict__ dapart, const float* __restrict__ a, float* __restrict__ ds, int T) {
-  extern __shared__ float sm[];   // [T]
-  __shared__ float red[4];
+  extern __shared__ double sd[];   // [T]
+  __shared__ double red[4];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  float dot = 0.f;
+  double dot = 0.0;
   for (int t = tid; t < T; t += 256) {
-    float da = 0.f;
-    for (int k = 0; k < kDaSlices; ++k) da += dapart[((size_t)b * kDaSlices + k) * T + t];
-    sm[t] = da;   // (only this thread touches column t)
-    dot = fmaf(a[(size_t)b * T + t], da, dot);
+    double da = 0.0;
+    for (int k = 0; k < kDaSlices; ++k) da += (double)dapart[((size_t)b * kDaSlices + k) * T + t];
+    sd[t] = da;   // (only this thread touches column t)
+    dot = fma((double)a[(size_t)b * T + t], da, dot);
   }
-  dot = mst::wave_sum(dot);
+  dot = wave_sum_d(dot);
   if (lane == 0) red[wave] = dot;
   __syncthreads();
   dot = (red[0] + red[1]) + (red[2] + red[3]);
-  for (int t = tid; t < T; t += 256) ds[(size_t)b * T + t] = a[(size_t)b * T + t] * (sm[t] - dot);
+  for (int t = tid; t < T; t += 256) ds[(size_t)b * T + t] = (float)((double)a[(size_t)b * T + t] * (sd[t] - dot));
 }
 // block = 64 rows m = (clip, frame): du[m][j] = ds[m] w2[j] (1 - h[m][j]^2);  per-block partial column sums of du (-> db0) and of
 // ds h (-> dw2), and the block's sum of ds (-> db2); thread = hidden unit j
 __global__ __launch_bounds__(256) void head_du_kernel(const float* __restrict__ h, const float* __restrict__ ds, const float* __restrict__ w2,
-                                                      float* __restrict__ du, float* __restrict__ part, int Mrows, int A) {
+                                                      float* __restrict__ du, double* __restrict__ part, int Mrows, int A) {
   const int j = threadIdx.x, m0 = blockIdx.x * 64;
-  float s_du = 0.f, s_dw = 0.f, s_ds = 0.f;
+  double s_du = 0.0, s_dw = 0.0, s_ds = 0.0;   // cancelling sums over the frames: in double, rounded once in the finish kernel
   if (j < A) {
     const float w = w2[j];
     for (int r = 0; r < 64; ++r) {
@@ -278,25 +306,25 @@ __global__ __launch_bounds__(256) void head_du_kernel(const float* __restrict__ 
       const float hv = h[(size_t)m * A + j], g = ds[m];
       const float v = g * w * (1.f - hv * hv);
       du[(size_t)m * A + j] = v;
-      s_du += v;
-      s_dw = fmaf(g, hv, s_dw);
-      s_ds += g;
+      s_du += (double)v;
+      s_dw = fma((double)g, (double)hv, s_dw);
+      s_ds += (double)g;
     }
   }
-  float* pb = part + (size_t)blockIdx.x * (2 * A + 1);
+  double* pb = part + (size_t)blockIdx.x * (2 * A + 1);
   if (j < A) pb[j] = s_du, pb[A + j] = s_dw;
   if (j == 0) pb[2 * A] = s_ds;
 }
 // second stage: fixed-order sums of the per-block partials
-__global__ __launch_bounds__(256) void head_du_finish_kernel(const float* __restrict__ part, int nblk, int A, float* __restrict__ db0,
+__global__ __launch_bounds__(256) void head_du_finish_kernel(const double* __restrict__ part, int nblk, int A, float* __restrict__ db0,
                                                              float* __restrict__ dw2, float* __restrict__ db2) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j > 2 * A) return;
-  float s = 0.f;
+  double s = 0.0;
   for (int k = 0; k < nblk; ++k) s += part[(size_t)k * (2 * A + 1) + j];
-  if (j < A) db0[j] = s;
-  else if (j < 2 * A) dw2[j - A] = s;
-  else db2[0] = s;
+  if (j < A) db0[j] = (float)s;
+  else if (j < 2 * A) dw2[j - A] = (float)s;
+  else db2[0] = (float)s;
 }
 
 // keep[i] = 1 iff element i survives a Dropout(p) keyed by `seed` (what every kernel above re-derives on the fly)
@@ -334,16 +362,20 @@ struct DxEpi {   // dx[z][c][t] = keep2 scale2 (v + a[z][t] dpooled[z][c])
 };
 
 // C = A B with the K range split over S workgroup slices: partial sums to `part` ([S][M][N]), then a fixed-order sum + epilogue
-template <bool AM, bool BN, class FA, class FB, class FIN>
+template <bool AM, bool BN, bool WIDE = false, class FA, class FB, class FIN>
 void gemm_split(int M, int N, int K, int S, FA fa, FB fb, float* part, FIN fin, hipStream_t st) {
   const int kslice = round_up((K + S - 1) / S, kKC);
   const int S2 = (K + kslice - 1) / kslice;
   PartEpi pe{part, M, N};
   hipLaunchKernelGGL((gemm_kernel<AM, BN, FA, FB, PartEpi>), dim3((N + 63) / 64, (M + 63) / 64, S2), dim3(256), 0, st, M, N, K, 1, kslice, fa, fb, pe);
   const long long cnt = (long long)M * N;
-  hipLaunchKernelGGL((splitk_finish_kernel<FIN>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, part, S2, cnt, fin);
+  hipLaunchKernelGGL((splitk_finish_kernel<WIDE, FIN>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, part, S2, cnt, fin);
 }
 constexpr int kSplitProj = 4, kSplitDW0 = 8, kSplitFilm = 8, kSplitHid = 4;
+// d h2 = d film Wh of the FiLM MLP sums over the out_dim = n_sub * 192 outputs (2112 in the model).  Its rounding is the largest
+// error of that backward (at B = 33 it put mlp.3.weight at 2.07 x the fp32 reference's own distance from float64, h1 contributing
+// half as much): cut into slices of at most 96 terms, added in double.
+constexpr int kSplitFilmOut = 32;
 
 struct HeadSave {   // offsets (floats) into the caller's save buffer
   size_t h, a, pooled, r, part, xd, hpart, total;
@@ -369,7 +401,7 @@ HeadWork head_work(int B, int C, int T, int A, int E) {
   auto take = [&](size_t n) { const size_t at = o; o += (n + 63) & ~(size_t)63; return at; };
   s.nblk = (B * T + 63) / 64;
   s.dz = take((size_t)B * E), s.dpooled = take((size_t)B * C), s.ds = take((size_t)B * T), s.du = take((size_t)B * T * A);
-  s.part = take((size_t)s.nblk * (2 * A + 1));
+  s.part = take((size_t)2 * s.nblk * (2 * A + 1));   // doubles
   s.gpart = take(std::max((size_t)kSplitDW0 * A * C, (size_t)kSplitProj * B * C));   // split-K partial sums
   s.dapart = take((size_t)B * kDaSlices * T);
   s.total = o;
@@ -377,7 +409,7 @@ HeadWork head_work(int B, int C, int T, int A, int E) {
 }
 }  // namespace
 
-// head_pool_kernel / head_ds_kernel / head_da_kernel keep T (4 T for head_da_kernel) floats in dynamic LDS: bounded here, in BOTH
+// head_pool_kernel / head_ds_kernel / head_da_kernel keep 12 T / 8 T / 16 T bytes in dynamic LDS: bounded here, in BOTH
 // entry points, so that an over-long clip is refused before any kernel of the pass has run (2048 pooled frames = 4 minutes of audio)
 constexpr int kHeadMaxFrames = 2048;
 static bool head_dims_ok(int C, int T, int A, int E) {
@@ -430,7 +462,7 @@ int mst_head_forward_train(const mst_head_dims* dm, const mst_head_weights* w, c
     // (split-K: 4 x the workgroups -- enough of them per CU to cover each other's load latency; the partial sums are 25 MB)
     gemm_split<true, false>(M, A, C, kSplitHid, fa, fb, sv + S.hpart, FinHid{sv + S.h, w->att0_b, A}, st);
   }
-  hipLaunchKernelGGL(head_pool_kernel, dim3(B, (C + 127) / 128), dim3(256), (size_t)T * sizeof(float), st, xd, sv + S.h, w->att2_w,
+  hipLaunchKernelGGL(head_pool_kernel, dim3(B, (C + 127) / 128), dim3(256), (size_t)T * (sizeof(double) + sizeof(float)), st, xd, sv + S.h, w->att2_w,
                      w->att2_b, sv + S.a, sv + S.pooled, C, T, A);
   // emb = Dropout(ReLU(pooled Wp^T + bp))
   gemm_split<false, false>(B, E, C, kSplitProj, RowMajA{sv + S.pooled, C}, RowMajT{w->proj_w, C}, sv + S.part, FinProj{emb, sv + S.r, w->proj_b, E, d3}, st);
@@ -463,9 +495,9 @@ int mst_head_backward(const mst_head_dims* dm, const mst_head_weights* w, const 
   gemm_split<false, true>(B, C, E, kSplitProj, RowMajA{ws + Wk.dz, E}, RowMajB{w->proj_w, C}, ws + Wk.gpart, FinStore{ws + Wk.dpooled}, st);   // dpooled = dz Wp
   // softmax / scores
   hipLaunchKernelGGL(head_da_kernel, dim3(B, kDaSlices), dim3(256), (size_t)4 * T * sizeof(float), st, xd, ws + Wk.dpooled, ws + Wk.dapart, C, T);
-  hipLaunchKernelGGL(head_ds_kernel, dim3(B), dim3(256), (size_t)T * sizeof(float), st, ws + Wk.dapart, sv + S.a, ws + Wk.ds, T);
-  hipLaunchKernelGGL(head_du_kernel, dim3(Wk.nblk), dim3(256), 0, st, sv + S.h, ws + Wk.ds, w->att2_w, ws + Wk.du, ws + Wk.part, M, A);
-  hipLaunchKernelGGL(head_du_finish_kernel, dim3((2 * A + 1 + 255) / 256), dim3(256), 0, st, ws + Wk.part, Wk.nblk, A, g->att0_b, g->att2_w, g->att2_b);
+  hipLaunchKernelGGL(head_ds_kernel, dim3(B), dim3(256), (size_t)T * sizeof(double), st, ws + Wk.dapart, sv + S.a, ws + Wk.ds, T);
+  hipLaunchKernelGGL(head_du_kernel, dim3(Wk.nblk), dim3(256), 0, st, sv + S.h, ws + Wk.ds, w->att2_w, ws + Wk.du, reinterpret_cast<double*>(ws + Wk.part), M, A);
+  hipLaunchKernelGGL(head_du_finish_kernel, dim3((2 * A + 1 + 255) / 256), dim3(256), 0, st, reinterpret_cast<const double*>(ws + Wk.part), Wk.nblk, A, g->att0_b, g->att2_w, g->att2_b);
   {   // dW0[j][c] = sum_m du[m][j] xd[m][c]
     DuT fa{ws + Wk.du, A};
     XdB fb{XdOp{xd, C, T}};
@@ -488,7 +520,7 @@ size_t mst_film_save_bytes(const mst_film_dims* d, int B) {
 }
 size_t mst_film_backward_workspace_bytes(const mst_film_dims* d, int B) {
   if (!d || B <= 0) return 0;
-  return (size_t)(2 + kSplitFilm) * B * d->hidden * sizeof(float);   // dh2, dh1, split-K partial sums
+  return (size_t)(2 + kSplitFilmOut) * B * d->hidden * sizeof(float);   // dh2, dh1, split-K partial sums
 }
 
 int mst_film_forward_train(const mst_film_dims* dm, const mst_film_weights* w, const float* feats, int B, float drop_p, uint64_t drop_seed,
@@ -518,6 +550,8 @@ int mst_film_backward(const mst_film_dims* dm, const mst_film_weights* w, const 
   MST_REQUIRE(dm && w && feats && dfilm && save && g && workspace && B > 0, "mst_film_backward: NULL / bad argument");
   MST_REQUIRE(g->mlp0_w && g->mlp0_b && g->mlp3_w && g->mlp3_b && g->head_w && g->head_b, "mst_film_backward: NULL gradient pointer");
   const int Fd = dm->feature_dim, H = dm->hidden, O = dm->out_dim;
+  MST_REQUIRE(Fd >= 1 && Fd <= 2048 && H >= 1 && H <= 2048 && O >= 1, "mst_film_backward: dims out of range (feature_dim=%d hidden=%d out_dim=%d; limits 2048, 2048)", Fd, H, O);
+  MST_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "mst_film_backward: dropout p must be in [0, 1)");
   if (workspace_bytes < mst_film_backward_workspace_bytes(dm, B)) return mst::fail(MST_ENOMEM, "mst_film_backward: workspace too small");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const float* h1d = static_cast<const float*>(save);
@@ -530,7 +564,7 @@ int mst_film_backward(const mst_film_dims* dm, const mst_film_weights* w, const 
   hipLaunchKernelGGL(colsum_kernel, dim3((O + 63) / 64), blk, 0, st, dfilm, g->head_b, B, O);
   hipLaunchKernelGGL((gemm_kernel<true, true, ColMajA, RowMajB, EpiStore>), dim3((H + 63) / 64, (O + 63) / 64, 1), blk, 0, st, O, H, B, 1,
                      round_up(B, kKC), ColMajA{dfilm, O}, RowMajB{h2, H}, EpiStore{g->head_w, H});   // dWh = dfilm^T h2
-  gemm_split<false, true>(B, H, O, kSplitFilm, RowMajA{dfilm, O}, RowMajB{w->head_w, H}, part, FinMask{dh2, h2, 1.f}, st);   // through the ReLU
+  gemm_split<false, true, true>(B, H, O, kSplitFilmOut, RowMajA{dfilm, O}, RowMajB{w->head_w, H}, part, FinMask{dh2, h2, 1.f}, st);   // through the ReLU
   // feature_mlp.3
   hipLaunchKernelGGL(colsum_kernel, dim3((H + 63) / 64), blk, 0, st, dh2, g->mlp3_b, B, H);
   hipLaunchKernelGGL((gemm_kernel<true, true, ColMajA, RowMajB, EpiStore>), dim3((H + 63) / 64, (H + 63) / 64, 1), blk, 0, st, H, H, B, 1,
@@ -550,7 +584,7 @@ int mst_film_backward(const mst_film_dims* dm, const mst_film_weights* w, const 
 // fixed-order sum, as in mst_film_backward.  Workspace: h1, h2, dh2, dh1 and the partial sums.
 size_t mst_film_input_grad_workspace_bytes(const mst_film_dims* d, int B) {
   if (!d || B <= 0) return 0;
-  return ((size_t)4 * B * d->hidden + (size_t)kSplitFilm * B * std::max(d->hidden, d->feature_dim)) * sizeof(float);
+  return ((size_t)4 * B * d->hidden + (size_t)kSplitFilmOut * B * std::max(d->hidden, d->feature_dim)) * sizeof(float);
 }
 
 int mst_film_input_grad(const mst_film_dims* dm, const mst_film_weights* w, const float* feats, int B, const float* dfilm, float* dfeats,
@@ -573,7 +607,7 @@ int mst_film_input_grad(const mst_film_dims* dm, const mst_film_weights* w, cons
   };
   linear(feats, w->mlp0_w, w->mlp0_b, h1, H, Fd);
   linear(h1, w->mlp3_w, w->mlp3_b, h2, H, H);
-  gemm_split<false, true>(B, H, O, kSplitFilm, RowMajA{dfilm, O}, RowMajB{w->head_w, H}, part, FinMask{dh2, h2, 1.f}, st);
+  gemm_split<false, true, true>(B, H, O, kSplitFilmOut, RowMajA{dfilm, O}, RowMajB{w->head_w, H}, part, FinMask{dh2, h2, 1.f}, st);
   gemm_split<false, true>(B, H, H, 2, RowMajA{dh2, H}, RowMajB{w->mlp3_w, H}, part, FinMask{dh1, h1, 1.f}, st);
   gemm_split<false, true>(B, Fd, H, 2, RowMajA{dh1, H}, RowMajB{w->mlp0_w, Fd}, part, FinStore{dfeats}, st);
   MST_HIP_CHECK(hipGetLastError());

@@ -117,58 +117,77 @@ __global__ __launch_bounds__(256) void infonce_reduce_kernel(const float* rowout
 }
 
 // rows kernel of the backward pass: recomputes S_i., then overwrites it with the coefficients c_i.
-__global__ __launch_bounds__(256) void infonce_coef_kernel(const float* emb, const int64_t* labels, const float* inv_norm,
-                                                           float* coef, int N, int D, int row0, float inv_tau) {
-  extern __shared__ float srow[];
-  __shared__ float red[12];
+// The scores, their exponentials and the two sums are formed in double from the raw rows (norms included): the coefficients are
+// softmax weights of scores up to 1 / tau, so an fp32 score carries 2^-24 / tau into every c_ij, and the gradient is a sum of
+// c_ij e_j that the normalisation then projects most of away (at D = 3 the fp32 coefficients put the gradient at twice the fp32
+// oracle's own distance from float64).  c_ij itself is stored in fp32.
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__global__ __launch_bounds__(256) void infonce_coef_kernel(const float* emb, const int64_t* labels, float* coef, int N, int D,
+                                                           int row0, float inv_tau) {
+  extern __shared__ float srow[];   // [D] the anchor row (raw)
+  __shared__ double red[12];
+  double* sc = reinterpret_cast<double*>(srow + ((D + 1) & ~1));   // [N] scores -> exponentials
   const int i = row0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float ni = inv_norm[i];
-  for (int d = tid; d < D; d += 256) srow[d] = emb[(size_t)i * D + d] * ni;
+  for (int d = tid; d < D; d += 256) srow[d] = emb[(size_t)i * D + d];
   __syncthreads();
+  auto inv_of = [](double sumsq) { return 1.0 / fmax(sqrt(sumsq), 1e-12); };   // F.normalize eps
+  double qi = 0.0;
+  for (int d = lane; d < D; d += 64) qi = fma((double)srow[d], (double)srow[d], qi);
+  const double ni = inv_of(wave_sum_d(qi));   // (every wave: the same bits)
   float* s = coef + (size_t)blockIdx.x * N;
-  float mx = -INFINITY;
+  double mx = -INFINITY;
   for (int j0 = wave * 4; j0 < N; j0 += 16) {
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    double a[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
     const float* ej[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) ej[u] = emb + (size_t)min(j0 + u, N - 1) * D;
     for (int d = lane; d < D; d += 64) {
-      const float x = srow[d];
+      const double x = (double)srow[d];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) a[u] = fmaf(x, ej[u][d], a[u]);
+      for (int u = 0; u < 4; ++u) {
+        const double v = (double)ej[u][d];
+        a[u] = fma(x, v, a[u]);
+        q[u] = fma(v, v, q[u]);
+      }
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int j = j0 + u;
       if (j >= N) break;
-      const float v = mst::wave_sum(a[u]) * inv_norm[j] * inv_tau;
-      if (lane == 0) s[j] = v;
-      mx = fmaxf(mx, v);
+      const double v = wave_sum_d(a[u]) * ni * inv_of(wave_sum_d(q[u])) * (double)inv_tau;
+      if (lane == 0) sc[j] = v;
+      mx = fmax(mx, v);
     }
   }
   if (lane == 0) red[wave] = mx;
   __syncthreads();
-  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
   const int64_t li = labels[i];
-  float pos = 0.f, neg = 0.f;
+  double pos = 0.0, neg = 0.0;
   for (int j = tid; j < N; j += 256) {
-    const float e = expf(s[j] - mx);
+    const double e = exp(sc[j] - mx);
+    sc[j] = e;   // (only this thread touches column j from here on)
     const bool same = labels[j] == li;
     if (same && j != i) pos += e;
     if (!same) neg += e;
   }
-  pos = mst::wave_sum(pos), neg = mst::wave_sum(neg);
+  pos = wave_sum_d(pos), neg = wave_sum_d(neg);
   if (lane == 0) red[4 + wave] = pos, red[8 + wave] = neg;
   __syncthreads();
   pos = (red[4] + red[5]) + (red[6] + red[7]);
   neg = (red[8] + red[9]) + (red[10] + red[11]);
-  const float inv_den = 1.0f / (pos + neg + 1e-8f), inv_pos = pos > 0.f ? 1.0f / pos : 0.f;
+  const bool has_pos = (float)pos > 0.f;   // the forward's test, on its fp32 sum
+  const double inv_den = 1.0 / (pos + neg + 1e-8), inv_pos = has_pos ? 1.0 / pos : 0.0;
   for (int j = tid; j < N; j += 256) {
-    const float e = expf(s[j] - mx);
+    const double e = sc[j];
     const bool same = labels[j] == li;
-    float c = 0.f;
-    if (pos > 0.f && j != i) c = e * inv_den - (same ? e * inv_pos : 0.f);
-    s[j] = c;
+    double c = 0.0;
+    if (has_pos && j != i) c = e * inv_den - (same ? e * inv_pos : 0.0);
+    s[j] = (float)c;
   }
 }
 
@@ -184,12 +203,14 @@ __global__ __launch_bounds__(256) void infonce_grad_kernel(const float* emb, con
   float dot = 0.f;
   const float nn = inv_norm[n];
   for (int d = tid; d < D; d += 256) {
-    float g = 0.f;
+    // up to 2 N signed terms that largely cancel: accumulated in double and rounded once (an fp32 chain of that length is
+    // 2.4 x as far from float64 as a blocked fp32 matrix product at N = 384, D = 768)
+    double acc = 0.0;
     if (local)
-      for (int j = 0; j < N; ++j) g = fmaf(crow[j], emb[(size_t)j * D + d] * inv_norm[j], g);
+      for (int j = 0; j < N; ++j) acc = fma((double)crow[j], (double)(emb[(size_t)j * D + d] * inv_norm[j]), acc);
     for (int i = 0; i < rows; ++i)
-      g = fmaf(coef[(size_t)i * N + n], emb[(size_t)(row0 + i) * D + d] * inv_norm[row0 + i], g);
-    g *= inv_tau;
+      acc = fma((double)coef[(size_t)i * N + n], (double)(emb[(size_t)(row0 + i) * D + d] * inv_norm[row0 + i]), acc);
+    const float g = (float)acc * inv_tau;
     sg[d] = g;
     dot = fmaf(g, emb[(size_t)n * D + d] * nn, dot);
   }
@@ -198,7 +219,7 @@ __global__ __launch_bounds__(256) void infonce_grad_kernel(const float* emb, con
   __syncthreads();
   dot = (red[0] + red[1]) + (red[2] + red[3]);
   const float sc = scale ? *scale : 1.0f;
-  for (int d = tid; d < D; d += 256) grad[(size_t)n * D + d] = sc * nn * (sg[d] - emb[(size_t)n * D + d] * nn * dot);
+  for (int d = tid; d < D; d += 256) grad[(size_t)n * D + d] = sc * (nn * (sg[d] - emb[(size_t)n * D + d] * nn * dot));   // the incoming factor last: k x the gradient to one rounding
 }
 
 }  // namespace
@@ -235,6 +256,9 @@ int mst_infonce_backward(const float* emb, const int64_t* labels, int N, int D, 
   MST_REQUIRE(emb && labels && grad, "mst_infonce_backward: NULL argument");
   MST_REQUIRE(N > 0 && D > 0 && row0 >= 0 && rows > 0 && row0 + rows <= N && temperature > 0.f,
               "mst_infonce_backward: bad sizes N=%d D=%d row0=%d rows=%d", N, D, row0, rows);
+  // infonce_coef_kernel keeps the anchor row and N scores (double) in dynamic LDS
+  const size_t coef_lds = (size_t)((D + 1) & ~1) * sizeof(float) + (size_t)N * sizeof(double);
+  MST_REQUIRE(coef_lds <= 64 * 1024, "mst_infonce_backward: 4 D + 8 N = %zu B of LDS, limit 65536 (N=%d D=%d)", coef_lds, N, D);
   const size_t need = mst_infonce_workspace_bytes(N, D);
   if (!workspace || workspace_bytes < need)
     return mst::fail(MST_ENOMEM, "mst_infonce_backward: workspace %zu B < required %zu B", workspace_bytes, need);
@@ -242,8 +266,7 @@ int mst_infonce_backward(const float* emb, const int64_t* labels, int N, int D, 
   float* inv_norm = reinterpret_cast<float*>(workspace);
   float* coef = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + mst::align_up((size_t)N * sizeof(float), 256));
   hipLaunchKernelGGL(l2norm_kernel, dim3(N), dim3(256), 0, st, emb, inv_norm, D);
-  hipLaunchKernelGGL(infonce_coef_kernel, dim3(rows), dim3(256), (size_t)D * sizeof(float), st, emb, labels, inv_norm, coef,
-                     N, D, row0, 1.0f / temperature);
+  hipLaunchKernelGGL(infonce_coef_kernel, dim3(rows), dim3(256), coef_lds, st, emb, labels, coef, N, D, row0, 1.0f / temperature);
   hipLaunchKernelGGL(infonce_grad_kernel, dim3(N), dim3(256), (size_t)D * sizeof(float), st, emb, inv_norm, coef, scale,
                      grad, N, D, row0, rows, 1.0f / temperature);
   MST_HIP_CHECK(hipGetLastError());
