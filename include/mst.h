@@ -663,6 +663,35 @@ int mst_tcn_film_forward(const mst_tcn_film* gen, const float* emb, int B, float
                          size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Stage C, streaming: block-wise inference of a CAUSAL mixer (csrc/tcn_stream.inc).  A push takes the next N samples of B
+ * streams and returns their N output samples.  The result does not depend on how the signal was cut into blocks: with the
+ * zero history a reset leaves, the pushes concatenated are the mst_tcn_forward result of the whole clip BIT FOR BIT (fp32
+ * mode).  The state is caller-owned device memory: the folded BatchNorm / FiLM table and, for every dilated convolution, a
+ * ring holding the last (K-1)*d samples of its input plus the block in flight (rounded up to a power of two of rows; at
+ * K = 15, num_blocks = 14, max_block = 16384 about 2^19 rows of H_padded floats per stream).  No allocation, no host
+ * synchronisation, everything on `stream`.  B, max_block and the handle must be those of the reset in every push.
+ * Refused (MST_EINVAL, the size queries return 0; mst_last_error names the way out): a non-causal mixer (it needs look-ahead:
+ * mst_tcn_forward), a handle in MST_TCN_F16X3 mode, B outside 1..65535, max_block < 1 or so large that a ring reaches
+ * 2^31 elements, N outside 1..max_block, t0 < 0, film not matching use_film; MST_ENOMEM for a state or workspace smaller
+ * than the size queries say.  After mst_tcn_update_params the state's folded table is stale: reset before the next push.
+ * FiLM is fixed per reset.  Not built: non-causal streaming with a fixed latency, f16x3 streaming, gradients.
+ * ------------------------------------------------------------------------------------------ */
+size_t mst_tcn_stream_state_bytes(const mst_tcn* tcn, int B, int max_block);
+size_t mst_tcn_stream_workspace_bytes(const mst_tcn* tcn, int B, int max_block);
+/* Zeroes every ring (the stream starts from zero history, which is the offline forward's padding) and folds the table
+ * from the handle's BatchNorm parameters and `film` (dev [B][num_blocks][4][H], required iff use_film).                  */
+int mst_tcn_stream_reset(const mst_tcn* tcn, void* state, size_t state_bytes, int B, int max_block, const float* film,
+                         void* stream);
+/* t0: samples pushed since the reset (the caller counts; 64-bit).  x, y: dev [B][8][N] fp32, y may not alias x.
+ * 2 * num_blocks + 2 kernel launches.                                                                                   */
+int mst_tcn_stream_push(const mst_tcn* tcn, void* state, size_t state_bytes, int B, int max_block, long long t0,
+                        const float* x, int N, float* y, void* workspace, size_t workspace_bytes, void* stream);
+/* The consecutive samples one wave of the convolution kernel owns in a push of N samples of B streams: 16, 32, or the
+ * offline kernel's 64 / 128.  Short blocks get the smaller tiles, so that they are spread over the chip's SIMDs; the result
+ * does not depend on the tile.  For the tests and the probe; 0 for a NULL handle or B, N < 1.                            */
+int mst_tcn_stream_samples_per_wave(const mst_tcn* tcn, int B, int N);
+
+/* ------------------------------------------------------------------------------------------
  * Stage C, training: the mixer in train() mode and its backward (src/train_style_transfer.py:255-317,
  * inference/test_tcn_style_transfer.py:84-200 back-propagate through it).  BatchNorm1d uses the batch statistics over
  * (B, T), biased variance; the whole batch goes through one call.  Exact fp32, fixed summation orders, no float atomics:

@@ -36,7 +36,9 @@ enum { EPI_ACT = 0, EPI_ACT_THEN_RES = 1, EPI_RES_THEN_ACT = 2 };
 // Accumulation is two-level: the products of ONE tap go into `part` (a chain of HP terms), and `part` is added to `acc`
 // once per tap.  One sequential fp32 chain over all K * HP terms (1920 at H = 128) rounds every step at the magnitude of
 // the running total and measured 3x the reference's own distance from float64; the two-level sum has 15 such roundings.
-template <int NT, int TT, int NO, bool EDGE, bool ODD>
+// RING (streaming, tcn_stream.inc): `inb` is a ring of T + 1 rows, T + 1 a power of two, and sample t lives in row t & T.
+// Only the row address differs: every row of a ring is readable and history before the stream's start is stored zeros.
+template <int NT, int TT, int NO, bool EDGE, bool ODD, bool RING = false>
 __device__ __forceinline__ void tcn_conv_tap(f32x4 (&acc)[NO][TT], const float* __restrict__ inb, const float* __restrict__ wt,
                                              int ts, int T, int j, int g, int o0) {
   constexpr int HP = NT * 16;
@@ -46,7 +48,7 @@ __device__ __forceinline__ void tcn_conv_tap(f32x4 (&acc)[NO][TT], const float* 
   for (int m = 0; m < TT; ++m) {
     const int t = ts + m * 16 + j;
     ok[m] = !EDGE || (t >= 0 && t < T);
-    const int tc = !EDGE ? t : (t < 0 ? 0 : (t >= T ? T - 1 : t));
+    const int tc = RING ? (t & T) : !EDGE ? t : (t < 0 ? 0 : (t >= T ? T - 1 : t));
     xrow[m] = inb + (tc * HP + 4 * g);
   }
   f32x4 part[NO][TT];
@@ -81,6 +83,16 @@ __device__ __forceinline__ void tcn_conv_tap(f32x4 (&acc)[NO][TT], const float* 
   for (int o = 0; o < NO; ++o)
 #pragma unroll
     for (int m = 0; m < TT; ++m) acc[o][m] += part[o][m];
+}
+
+// The folded epilogue of one output element: S * acc + C, LeakyReLU, residual in the order of
+// the block type.  One spelling for the offline and the streaming kernel, whose results must agree bit for bit.
+__device__ __forceinline__ float tcn_conv_epilogue(float acc, float S, float Cc, float r, int epi) {
+  float z = fmaf(S, acc, Cc);
+  if (epi == EPI_RES_THEN_ACT) z += r;
+  z = leaky(z);
+  if (epi == EPI_ACT_THEN_RES) z += r;
+  return z;
 }
 
 // in/out/res: one buffer of [B][T][HP].  wsw: [K][NT chunk][NT out tile][64 lanes][4] of this convolution.
@@ -133,17 +145,7 @@ __global__ __launch_bounds__(256, 2) void tcn_conv_kernel(const float* __restric
       f32x4 v = acc[o][m], r = f32x4{0.f, 0.f, 0.f, 0.f};
       if (RAW ? res != nullptr : epi != EPI_ACT) r = *reinterpret_cast<const f32x4*>(res + at);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (RAW) {
-          v[q] = (v[q] + Cc[q]) + r[q];
-          continue;
-        }
-        float z = fmaf(S[q], v[q], Cc[q]);
-        if (epi == EPI_RES_THEN_ACT) z += r[q];
-        z = leaky(z);
-        if (epi == EPI_ACT_THEN_RES) z += r[q];
-        v[q] = z;
-      }
+      for (int q = 0; q < 4; ++q) v[q] = RAW ? (v[q] + Cc[q]) + r[q] : tcn_conv_epilogue(v[q], S[q], Cc[q], r[q], epi);
       *reinterpret_cast<f32x4*>(out + at) = v;
     }
   }
@@ -541,3 +543,4 @@ int mst_tcn_film_forward(const mst_tcn_film* f, const float* emb, int B, float* 
 
 #include "tcn_f16x3.inc"
 #include "tcn_train.inc"
+#include "tcn_stream.inc"

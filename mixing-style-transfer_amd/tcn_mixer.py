@@ -20,6 +20,10 @@ Same class names, constructor arguments, defaults and `state_dict` keys as the r
     function on the module's live parameters: Dropout from seeds of torch's CPU generator, all six parameter gradients and,
     when the embedding requires one, its gradient.  `eval()` without gradients stays on the inference handle.
 
+`TCNMixer.stream()` returns a `TCNStream`: block-wise inference of a causal mixer on audio as it arrives (`push`, `reset`,
+`position`), on the kernels of `csrc/tcn_stream.inc` with `backend = "hip"` (bit-equal to the whole-clip forward whatever the
+block sizes) or on history tensors with `backend = "torch"`.
+
 `optimize_tcn_style_transfer` is the reference's per-pair fit (inference/test_tcn_style_transfer.py:84-201) on these backends and
 `mst_amd.optim`, without a host synchronisation inside its loop.
 """
@@ -592,10 +596,182 @@ class TCNMixer(nn.Module):
         film = _packed_film(film_params, x.shape[0], self.num_blocks, self.hidden_channels) if self.use_film else None
         return self._forward_hip(x, film)[0]
 
+    def stream(self, batch_size=1, max_block=4096, film_params=None):
+        """A `TCNStream`: block-wise inference of this (causal) mixer on audio as it arrives.  `film_params` as `forward`
+        takes them, fixed until the next `reset`."""
+        return TCNStream(self, batch_size, max_block, film_params)
+
     def process_stems_dict(self, stems_dict, film_params=None):
         stacked = torch.cat([stems_dict[s] for s in STEM_ORDER], dim=0).unsqueeze(0)
         out = self.forward(stacked, film_params=film_params).squeeze(0)
         return {s: out[2 * i:2 * i + 2, :] for i, s in enumerate(STEM_ORDER)}
+
+
+class TCNStream:
+    """Block-wise inference of a causal `TCNMixer` on audio as it arrives (`TCNMixer.stream`).
+
+    `push(x)` takes the next N samples, (B, 8, N) with 1 <= N <= max_block, and returns their N output samples.  Every
+    dilated convolution keeps the last (K-1)*d samples of its own input, zeros at the start, so the pushes concatenated are
+    the whole-clip `mixer(x, film_params)` whatever the block sizes: bit for bit on `backend="hip"` (the kernels of
+    csrc/tcn_stream.inc run the offline kernels' arithmetic on ring buffers), to rounding on `backend="torch"` (torch
+    picks its summation order by length).  FiLM is fixed per `reset`.  The stream binds the mixer's parameters and buffers
+    as they are at `stream()` / `reset()`: a push after any of them changed raises and names `reset()`.
+
+    `backend="hip"` needs eval(), causal=True, precision="fp32", CUDA fp32 input and no gradients, makes no host
+    synchronisation and allocates its state once (`state_bytes`); `backend="torch"` is the plain restatement (history
+    tensors concatenated in front of the block; any device and dtype, eval() only, no gradients) and the explicit opt-in for
+    everything else.  A non-causal mixer and `backend="hip-train"` raise.  `position`: samples pushed since position 0."""
+
+    def __init__(self, mixer, batch_size=1, max_block=4096, film_params=None):
+        if int(batch_size) < 1 or int(max_block) < 1:
+            raise ValueError(f"TCNMixer.stream: batch_size and max_block must be positive, got {batch_size}, {max_block}")
+        self.mixer, self.batch_size, self.max_block = mixer, int(batch_size), int(max_block)
+        self.position = 0
+        self._film_params = self._state = self._work = None
+        self.reset(film_params)
+
+    # ---- what both backends refuse -----------------------------------------------------------------------------------
+    def _check_mixer(self, what):
+        m = self.mixer
+        if m.backend not in _MIXER_BACKENDS:
+            raise ValueError("backend must be 'hip' (default), 'torch' or 'hip-train'")
+        if not m.causal:
+            raise RuntimeError(f"{what}: streaming needs a causal mixer (causal=True); a non-causal one looks ahead ((K-1)*d)//2 "
+                               f"samples per layer, which a block-wise call does not have: evaluate whole clips with TCNMixer.forward")
+        if m.backend == "hip-train":
+            raise RuntimeError(f"{what}: backend='hip-train' is the training path and streaming is inference only; set "
+                               f"backend='hip' (or 'torch')")
+        if m.training:
+            msg = f"{what}: streaming is inference only and the module is in train() mode (batch statistics depend on the block); call eval()"
+            if m.backend == "hip":
+                _raise_refusal(msg)
+            raise RuntimeError(msg)
+        if m.backend == "hip":
+            if m.precision not in _PRECISIONS:
+                raise ValueError(f"precision must be 'fp32' (default) or 'f16x3', got {m.precision!r}")
+            if m.precision != "fp32":
+                _raise_refusal(f"{what}: precision={m.precision!r} cannot stream (its per-clip range scale is a function of the "
+                               f"whole clip); set precision='fp32'")
+
+    @property
+    def state_bytes(self):
+        """Device bytes of the HIP state (0 on backend='torch' before the first push allocates its history tensors)."""
+        return 0 if self._state is None else self._state.numel()
+
+    def reset(self, film_params=None, position=0):
+        """Zero history; new FiLM parameters if given (else those of the last reset); `position` = sample index of the next
+        push.  Binds the mixer's current parameters and buffers."""
+        m = self.mixer
+        self._check_mixer("TCNStream.reset")
+        if int(position) < 0:
+            raise ValueError(f"TCNStream.reset: position must not be negative, got {position}")
+        film_params = self._film_params if film_params is None else film_params
+        if m.use_film:
+            if film_params is None:
+                raise ValueError("film_params must be provided when use_film=True")
+            if len(film_params) != m.num_blocks:
+                raise ValueError(f"Expected {m.num_blocks} FiLM parameter dicts, got {len(film_params)}")
+        elif film_params is not None:
+            raise ValueError("film_params given for a mixer with use_film=False")
+        self._backend = m.backend
+        self._hist = None
+        if m.backend == "hip":
+            self._reset_hip(film_params)
+        self._film_params = film_params
+        self._key = _state_key(m)
+        self.position = int(position)
+
+    def _reset_hip(self, film_params):
+        m, B = self.mixer, self.batch_size
+        what = "TCNStream.reset"
+        fl = [p[k] for p in film_params for k in _FILM_KEYS] if m.use_film else []
+        dev = m.input_conv.weight.device
+        msg = _tensor_refusal(what, m.input_conv.weight, *fl)
+        if msg is None and any(t.device != dev for t in fl):
+            msg = f"{what}: the mixer is on {dev} and a FiLM tensor on another device; the kernels need one device"
+        if msg:
+            _raise_refusal(msg)
+        h = m._handle(dev)
+        film = _packed_film(film_params, B, m.num_blocks, m.hidden_channels) if m.use_film else None
+        if film is not None and tuple(film.shape) != (B, m.num_blocks, 4, m.hidden_channels):
+            raise ValueError(f"expected FiLM tensors of shape ({B}, {m.hidden_channels}), got a stack of {tuple(film.shape)}")
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            if getattr(h, "precision", "fp32") != "fp32":
+                _lib.check(L.mst_tcn_set_precision(h.ptr, _PRECISIONS["fp32"], _lib.stream_ptr(dev)), "mst_tcn_set_precision")
+                h.precision = "fp32"
+            nstate = L.mst_tcn_stream_state_bytes(h.ptr, B, self.max_block)
+            nwork = L.mst_tcn_stream_workspace_bytes(h.ptr, B, self.max_block)
+            if nstate == 0 or nwork == 0:
+                _lib.check(-1, "mst_tcn_stream_state_bytes")
+            if self._state is None or self._state.numel() != nstate or self._state.device != dev:
+                self._state = self._work = None
+                self._state = torch.empty(nstate, device=dev, dtype=torch.uint8)
+                self._work = torch.empty(nwork, device=dev, dtype=torch.uint8)
+            _lib.check(L.mst_tcn_stream_reset(h.ptr, _lib.dptr(self._state), nstate, B, self.max_block, _lib.dptr(film),
+                                              _lib.stream_ptr(dev)), "mst_tcn_stream_reset")
+        self._handle = h   # (keeps the C handle alive while the stream uses it)
+
+    def push(self, x):
+        """x (B, 8, N), 1 <= N <= max_block -> (B, 8, N), the next N output samples."""
+        m = self.mixer
+        self._check_mixer("TCNStream.push")
+        if m.backend != self._backend or _state_key(m) != self._key:
+            raise RuntimeError("TCNStream.push: the mixer's backend, parameters or buffers changed since the stream was bound "
+                               "(load_state_dict, .to(), an in-place edit, an optimiser step); the carried history and the folded "
+                               "BatchNorm / FiLM table belong to the old ones: call reset()")
+        if x.dim() != 3 or x.shape[1] != m.in_channels:
+            raise ValueError(f"expected (B, {m.in_channels}, N) stems, got {tuple(x.shape)}")
+        B, _, N = x.shape
+        if B != self.batch_size:
+            raise ValueError(f"TCNStream.push: the stream was made for batch_size={self.batch_size}, got a batch of {B}")
+        if N < 1 or N > self.max_block:
+            raise ValueError(f"TCNStream.push: a block holds 1..max_block={self.max_block} samples, got {N}")
+        y = self._push_hip(x) if m.backend == "hip" else self._push_torch(x)
+        self.position += N
+        return y
+
+    def _push_hip(self, x):
+        m = self.mixer
+        msg = _hip_refusal(m, "TCNStream.push", x)
+        if msg is None and x.device != self._state.device:
+            msg = f"TCNStream.push: the stream's state is on {self._state.device} and x on {x.device}"
+        if msg:
+            _raise_refusal(msg)
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        dev, L = x.device, _lib.lib()
+        with torch.cuda.device(dev):
+            _lib.check(L.mst_tcn_stream_push(self._handle.ptr, _lib.dptr(self._state), self._state.numel(), self.batch_size,
+                                             self.max_block, self.position, _lib.dptr(x), x.shape[2], _lib.dptr(y),
+                                             _lib.dptr(self._work), self._work.numel(), _lib.stream_ptr(dev)), "mst_tcn_stream_push")
+        return y
+
+    def _push_torch(self, x):
+        m, film = self.mixer, self._film_params
+        N = x.shape[2]
+        with torch.no_grad():
+            if self._hist is None:
+                self._hist = [x.new_zeros(x.shape[0], m.hidden_channels, (m.kernel_size - 1) * 2 ** (i // 2))
+                              for i in range(2 * m.num_blocks)]
+
+            def conv(c, h, i):   # the causal convolution on (its history, the block); keeps the last (K-1)*d input samples
+                z = torch.cat([self._hist[i], h], dim=2)
+                self._hist[i] = z[:, :, N:]
+                return F.conv1d(z, c.conv.weight, c.conv.bias, dilation=c.conv.dilation)
+
+            h = m.input_conv(x)
+            for i, blk in enumerate(m.blocks):
+                g = blk.norm1(conv(blk.conv1, h, 2 * i))
+                if m.use_film:
+                    p = film[i]
+                    g = F.leaky_relu(p["gamma1"].unsqueeze(-1) * g + p["beta1"].unsqueeze(-1), negative_slope=0.2)
+                    g = blk.norm2(conv(blk.conv2, g, 2 * i + 1))
+                    h = F.leaky_relu(p["gamma2"].unsqueeze(-1) * g + p["beta2"].unsqueeze(-1), negative_slope=0.2) + h
+                else:
+                    g = blk.norm2(conv(blk.conv2, F.leaky_relu(g, negative_slope=0.2), 2 * i + 1))
+                    h = F.leaky_relu(g + h, negative_slope=0.2)
+            return m.output_conv(h) + x
 
 
 class _TCNTrainFn(torch.autograd.Function):
