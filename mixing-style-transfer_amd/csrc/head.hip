@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstdint>
 
 #include "common.h"
@@ -407,6 +408,99 @@ HeadWork head_work(int B, int C, int T, int A, int E) {
   s.total = o;
   return s;
 }
+
+// ------------------------------------------------------------------------------------------
+// Linear -> act -> Dropout -> Linear -> act -> Dropout -> Linear: the FiLM MLP, the discriminator and the TCN FiLM generator.
+// One description of a call, one forward chain, one backward chain; an entry point states its finish functors and split counts.
+// ------------------------------------------------------------------------------------------
+struct Mlp {   // one call: B rows through I -> H -> H -> O, weights [out][in] (state_dict layout); fn = the entry point, for messages
+  const char* fn;
+  int B, I, H, O;
+  const float *w[3], *b[3];
+};
+struct MlpGrads { float *w[3], *b[3]; };
+struct MlpLimits { const char *in, *hid; int I, H, O, B; };   // names of the first two dims in the public struct, largest sizes
+// (the public dims / weights / grads structs of the three networks are three ints / six pointers w, b, w, b, w, b each)
+template <class D, class W>
+Mlp mlp_net(const char* fn, const D* d, const W* w, int B) {
+  const auto [I, H, O] = *d;
+  const auto [w0, b0, w1, b1, w2, b2] = *w;
+  return Mlp{fn, B, I, H, O, {w0, w1, w2}, {b0, b1, b2}};
+}
+template <class G>
+MlpGrads mlp_grads(const G* g) {
+  const auto [w0, b0, w1, b1, w2, b2] = *g;
+  return MlpGrads{{w0, w1, w2}, {b0, b1, b2}};
+}
+bool mlp_dims_ok(const MlpLimits& l, int I, int H, int O) { return I >= 1 && I <= l.I && H >= 1 && H <= l.H && O >= 1 && O <= l.O; }
+template <class D>
+bool mlp_in_limits(const MlpLimits& l, const D* d, int B) {   // (the *_bytes functions answer 0 for a call the entry points refuse)
+  if (!d) return false;
+  const auto [I, H, O] = *d;
+  return B >= 1 && B <= l.B && mlp_dims_ok(l, I, H, O);
+}
+// what every entry point refuses, under its own name (g: the gradient pointers of a backward, else NULL)
+int mlp_check(const Mlp& n, const MlpLimits& l, const MlpGrads* g, float p1, float p2) {
+  MST_REQUIRE(n.w[0] && n.b[0] && n.w[1] && n.b[1] && n.w[2] && n.b[2], "%s: NULL weight", n.fn);
+  MST_REQUIRE(!g || (g->w[0] && g->b[0] && g->w[1] && g->b[1] && g->w[2] && g->b[2]), "%s: NULL gradient pointer", n.fn);
+  MST_REQUIRE(mlp_dims_ok(l, n.I, n.H, n.O), "%s: dims out of range (%s=%d in 1..%d, %s=%d in 1..%d, out_dim=%d in 1..%d)", n.fn, l.in, n.I, l.I,
+              l.hid, n.H, l.H, n.O, l.O);
+  MST_REQUIRE(n.B >= 1 && n.B <= l.B, "%s: B=%d rows, must be in 1..%d", n.fn, n.B, l.B);
+  MST_REQUIRE(p1 >= 0.f && p1 < 1.f && p2 >= 0.f && p2 < 1.f, "%s: dropout p must be in [0, 1)", n.fn);
+  return MST_OK;
+}
+// a save buffer or a workspace (offsets in floats): nt tensors of B x H, then S slices of B x W split-K partial sums
+struct MlpBuf {
+  size_t bh, part, total;
+  size_t at(int i) const { return i * bh; }
+};
+MlpBuf mlp_buf(int B, int H, int nt, int S, int W) {
+  MlpBuf s{(size_t)B * H, (size_t)nt * B * H, 0};
+  s.total = s.part + (size_t)S * B * W;
+  return s;
+}
+int mlp_room(const char* fn, const char* what, size_t have, const MlpBuf& need) {
+  if (have < need.total * sizeof(float)) return mst::fail(MST_ENOMEM, "%s: %s %zu B < %zu B", fn, what, have, need.total * sizeof(float));
+  return MST_OK;
+}
+// out = fin(X W^T) for X [B][K], W [N][K]: split-K over S slices with the bias / activation / Dropout in the finish kernel, or
+// (a LinEpi) one GEMM over all of K with them in its epilogue
+template <class FIN>
+void linear(const float* X, int K, const float* W, int N, int B, int S, float* part, FIN fin, hipStream_t st) {
+  gemm_split<false, false>(B, N, K, S, RowMajA{X, K}, RowMajT{W, K}, part, fin, st);
+}
+void linear(const float* X, int K, const float* W, int N, int B, int, float*, LinEpi epi, hipStream_t st) {
+  hipLaunchKernelGGL((gemm_kernel<false, false, RowMajA, RowMajT, LinEpi>), dim3((N + 63) / 64, (B + 63) / 64, 1), dim3(256), 0, st, B, N, K, 1,
+                     round_up(K, kKC), RowMajA{X, K}, RowMajT{W, K}, epi);
+}
+// db = colsum(dy), dw = dy^T in   for dy [B][N], in [B][K]
+void linear_wgrad(const float* dy, int N, const float* in, int K, float* dw, float* db, int B, hipStream_t st) {
+  hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64), dim3(256), 0, st, dy, db, B, N);
+  hipLaunchKernelGGL((gemm_kernel<true, true, ColMajA, RowMajB, EpiStore>), dim3((K + 63) / 64, (N + 63) / 64, 1), dim3(256), 0, st, N, K, B, 1,
+                     round_up(B, kKC), ColMajA{dy, N}, RowMajB{in, K}, EpiStore{dw, K});
+}
+// f1 / f2 write the activations h1 / h2 ([B][H]) that the next layer reads, f3 the output
+template <class F1, class F2, class F3>
+void mlp_forward(const Mlp& n, const float* x, const float* h1, const float* h2, int S, float* part, F1 f1, F2 f2, F3 f3, hipStream_t st) {
+  linear(x, n.I, n.w[0], n.H, n.B, S, part, f1, st);
+  linear(h1, n.H, n.w[1], n.H, n.B, S, part, f2, st);
+  linear(h2, n.H, n.w[2], n.O, n.B, S, part, f3, st);
+}
+// dy [B][O] back through the three layers: m2 / m1 take d h2 / d h1 through the activation and Dropout in front of the layer and
+// write them to dh2 / dh1; weight gradients if g, input gradient if dx.  S2 / S1 / S0: split counts of the three products
+// (WIDE2: the slices of d h2 are added in double)
+template <bool WIDE2, class M2, class M1>
+void mlp_backward(const Mlp& n, const float* x, const float* h1, const float* h2, const float* dy, const MlpGrads* g, float* dx, const float* dh2,
+                  const float* dh1, float* part, int S2, M2 m2, int S1, M1 m1, int S0, hipStream_t st) {
+  if (g) linear_wgrad(dy, n.O, h2, n.H, g->w[2], g->b[2], n.B, st);
+  gemm_split<false, true, WIDE2>(n.B, n.H, n.O, S2, RowMajA{dy, n.O}, RowMajB{n.w[2], n.H}, part, m2, st);
+  if (g) linear_wgrad(dh2, n.H, h1, n.H, g->w[1], g->b[1], n.B, st);
+  gemm_split<false, true>(n.B, n.H, n.H, S1, RowMajA{dh2, n.H}, RowMajB{n.w[1], n.H}, part, m1, st);
+  if (g) linear_wgrad(dh1, n.H, x, n.I, g->w[0], g->b[0], n.B, st);
+  if (dx) gemm_split<false, true>(n.B, n.I, n.H, S0, RowMajA{dh1, n.H}, RowMajB{n.w[0], n.I}, part, FinStore{dx}, st);
+}
+// FiLM MLP: dims <= 2048 (mst.h), any B
+const MlpLimits kFilmLimits{"feature_dim", "hidden", 2048, 2048, INT_MAX, INT_MAX};
 }  // namespace
 
 // head_pool_kernel / head_ds_kernel / head_da_kernel keep 12 T / 8 T / 16 T bytes in dynamic LDS: bounded here, in BOTH
@@ -489,9 +583,7 @@ int mst_head_backward(const mst_head_dims* dm, const mst_head_weights* w, const 
   const float* xd = d2.thresh ? sv + S.xd : pool_in;
   // projection
   hipLaunchKernelGGL(head_dz_kernel, dim3((unsigned)(((long long)B * E + 255) / 256)), dim3(256), 0, st, demb, sv + S.r, ws + Wk.dz, (long long)B * E, d3);
-  hipLaunchKernelGGL(colsum_kernel, dim3((E + 63) / 64), dim3(256), 0, st, ws + Wk.dz, g->proj_b, B, E);
-  hipLaunchKernelGGL((gemm_kernel<true, true, ColMajA, RowMajB, EpiStore>), dim3((C + 63) / 64, (E + 63) / 64, 1), dim3(256), 0, st, E, C, B, 1,
-                     round_up(B, kKC), ColMajA{ws + Wk.dz, E}, RowMajB{sv + S.pooled, C}, EpiStore{g->proj_w, C});   // dWp = dz^T pooled
+  linear_wgrad(ws + Wk.dz, E, sv + S.pooled, C, g->proj_w, g->proj_b, B, st);   // dWp = dz^T pooled
   gemm_split<false, true>(B, C, E, kSplitProj, RowMajA{ws + Wk.dz, E}, RowMajB{w->proj_w, C}, ws + Wk.gpart, FinStore{ws + Wk.dpooled}, st);   // dpooled = dz Wp
   // softmax / scores
   hipLaunchKernelGGL(head_da_kernel, dim3(B, kDaSlices), dim3(256), (size_t)4 * T * sizeof(float), st, xd, ws + Wk.dpooled, ws + Wk.dapart, C, T);
@@ -516,65 +608,42 @@ int mst_head_backward(const mst_head_dims* dm, const mst_head_weights* w, const 
 
 size_t mst_film_save_bytes(const mst_film_dims* d, int B) {
   if (!d || B <= 0) return 0;
-  return (size_t)2 * B * d->hidden * sizeof(float);
+  return mlp_buf(B, d->hidden, 2, 0, 0).total * sizeof(float);   // h1 (dropped), h2
 }
 size_t mst_film_backward_workspace_bytes(const mst_film_dims* d, int B) {
   if (!d || B <= 0) return 0;
-  return (size_t)(2 + kSplitFilmOut) * B * d->hidden * sizeof(float);   // dh2, dh1, split-K partial sums
+  return mlp_buf(B, d->hidden, 2, kSplitFilmOut, d->hidden).total * sizeof(float);   // dh2, dh1, split-K partial sums
 }
 
 int mst_film_forward_train(const mst_film_dims* dm, const mst_film_weights* w, const float* feats, int B, float drop_p, uint64_t drop_seed,
                            float* film, void* save, size_t save_bytes, void* stream) {
-  MST_REQUIRE(dm && w && feats && film && save && B > 0, "mst_film_forward_train: NULL / bad argument");
-  MST_REQUIRE(w->mlp0_w && w->mlp0_b && w->mlp3_w && w->mlp3_b && w->head_w && w->head_b, "mst_film_forward_train: NULL weight");
-  const int Fd = dm->feature_dim, H = dm->hidden, O = dm->out_dim;
-  MST_REQUIRE(Fd >= 1 && Fd <= 2048 && H >= 1 && H <= 2048 && O >= 1, "mst_film_forward_train: dims out of range");
-  MST_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "mst_film_forward_train: dropout p must be in [0, 1)");
-  if (save_bytes < mst_film_save_bytes(dm, B)) return mst::fail(MST_ENOMEM, "mst_film_forward_train: save buffer too small");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  float* h1d = static_cast<float*>(save);
-  float* h2 = h1d + (size_t)B * H;
-  auto linear = [&](const float* X, const float* W, const float* bias, float* out, int N, int K, int relu, Drop d) {   // out = act(X W^T + b)
-    hipLaunchKernelGGL((gemm_kernel<false, false, RowMajA, RowMajT, LinEpi>), dim3((N + 63) / 64, (B + 63) / 64, 1), dim3(256), 0, st, B, N, K, 1,
-                       round_up(K, kKC), RowMajA{X, K}, RowMajT{W, K}, LinEpi{out, bias, N, relu, d});
-  };
-  linear(feats, w->mlp0_w, w->mlp0_b, h1d, H, Fd, 1, make_drop(drop_p, drop_seed));
-  linear(h1d, w->mlp3_w, w->mlp3_b, h2, H, H, 1, make_drop(0.f, 0));
-  linear(h2, w->head_w, w->head_b, film, O, H, 0, make_drop(0.f, 0));
+  MST_REQUIRE(dm && w && feats && film && save, "mst_film_forward_train: NULL argument");
+  const Mlp n = mlp_net("mst_film_forward_train", dm, w, B);
+  if (const int rc = mlp_check(n, kFilmLimits, nullptr, drop_p, 0.f)) return rc;
+  const MlpBuf S = mlp_buf(B, n.H, 2, 0, 0);
+  if (const int rc = mlp_room(n.fn, "save buffer", save_bytes, S)) return rc;
+  float* h1d = static_cast<float*>(save) + S.at(0);
+  float* h2 = static_cast<float*>(save) + S.at(1);
+  const Drop d0 = make_drop(0.f, 0);   // (Dropout behind the first layer only)
+  mlp_forward(n, feats, h1d, h2, 0, nullptr, LinEpi{h1d, n.b[0], n.H, 1, make_drop(drop_p, drop_seed)}, LinEpi{h2, n.b[1], n.H, 1, d0},
+              LinEpi{film, n.b[2], n.O, 0, d0}, reinterpret_cast<hipStream_t>(stream));
   MST_HIP_CHECK(hipGetLastError());
   return MST_OK;
 }
 
 int mst_film_backward(const mst_film_dims* dm, const mst_film_weights* w, const float* feats, int B, float drop_p, const float* dfilm,
                       const void* save, const mst_film_grads* g, void* workspace, size_t workspace_bytes, void* stream) {
-  MST_REQUIRE(dm && w && feats && dfilm && save && g && workspace && B > 0, "mst_film_backward: NULL / bad argument");
-  MST_REQUIRE(g->mlp0_w && g->mlp0_b && g->mlp3_w && g->mlp3_b && g->head_w && g->head_b, "mst_film_backward: NULL gradient pointer");
-  const int Fd = dm->feature_dim, H = dm->hidden, O = dm->out_dim;
-  MST_REQUIRE(Fd >= 1 && Fd <= 2048 && H >= 1 && H <= 2048 && O >= 1, "mst_film_backward: dims out of range (feature_dim=%d hidden=%d out_dim=%d; limits 2048, 2048)", Fd, H, O);
-  MST_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "mst_film_backward: dropout p must be in [0, 1)");
-  if (workspace_bytes < mst_film_backward_workspace_bytes(dm, B)) return mst::fail(MST_ENOMEM, "mst_film_backward: workspace too small");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const float* h1d = static_cast<const float*>(save);
-  const float* h2 = h1d + (size_t)B * H;
-  float* dh2 = static_cast<float*>(workspace);
-  float* dh1 = dh2 + (size_t)B * H;
-  float* part = dh1 + (size_t)B * H;
-  const dim3 blk(256);
-  // film_head
-  hipLaunchKernelGGL(colsum_kernel, dim3((O + 63) / 64), blk, 0, st, dfilm, g->head_b, B, O);
-  hipLaunchKernelGGL((gemm_kernel<true, true, ColMajA, RowMajB, EpiStore>), dim3((H + 63) / 64, (O + 63) / 64, 1), blk, 0, st, O, H, B, 1,
-                     round_up(B, kKC), ColMajA{dfilm, O}, RowMajB{h2, H}, EpiStore{g->head_w, H});   // dWh = dfilm^T h2
-  gemm_split<false, true, true>(B, H, O, kSplitFilmOut, RowMajA{dfilm, O}, RowMajB{w->head_w, H}, part, FinMask{dh2, h2, 1.f}, st);   // through the ReLU
-  // feature_mlp.3
-  hipLaunchKernelGGL(colsum_kernel, dim3((H + 63) / 64), blk, 0, st, dh2, g->mlp3_b, B, H);
-  hipLaunchKernelGGL((gemm_kernel<true, true, ColMajA, RowMajB, EpiStore>), dim3((H + 63) / 64, (H + 63) / 64, 1), blk, 0, st, H, H, B, 1,
-                     round_up(B, kKC), ColMajA{dh2, H}, RowMajB{h1d, H}, EpiStore{g->mlp3_w, H});
-  // through Dropout and ReLU: the survivors are exactly the positive entries of the dropped activation
-  gemm_split<false, true>(B, H, H, 2, RowMajA{dh2, H}, RowMajB{w->mlp3_w, H}, part, FinMask{dh1, h1d, drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f}, st);
-  // feature_mlp.0
-  hipLaunchKernelGGL(colsum_kernel, dim3((H + 63) / 64), blk, 0, st, dh1, g->mlp0_b, B, H);
-  hipLaunchKernelGGL((gemm_kernel<true, true, ColMajA, RowMajB, EpiStore>), dim3((Fd + 63) / 64, (H + 63) / 64, 1), blk, 0, st, H, Fd, B, 1,
-                     round_up(B, kKC), ColMajA{dh1, H}, RowMajB{feats, Fd}, EpiStore{g->mlp0_w, Fd});
+  MST_REQUIRE(dm && w && feats && dfilm && save && g && workspace, "mst_film_backward: NULL argument");
+  const Mlp n = mlp_net("mst_film_backward", dm, w, B);
+  const MlpGrads G = mlp_grads(g);
+  if (const int rc = mlp_check(n, kFilmLimits, &G, drop_p, 0.f)) return rc;
+  const MlpBuf S = mlp_buf(B, n.H, 2, 0, 0), Wk = mlp_buf(B, n.H, 2, kSplitFilmOut, n.H);
+  if (const int rc = mlp_room(n.fn, "workspace", workspace_bytes, Wk)) return rc;
+  const float *sv = static_cast<const float*>(save), *h1d = sv + S.at(0), *h2 = sv + S.at(1);
+  float *ws = static_cast<float*>(workspace), *dh2 = ws + Wk.at(0), *dh1 = ws + Wk.at(1);
+  // d h2 through the ReLU; d h1 through Dropout and ReLU: the survivors are exactly the positive entries of the dropped activation
+  mlp_backward<true>(n, feats, h1d, h2, dfilm, &G, nullptr, dh2, dh1, ws + Wk.part, kSplitFilmOut, FinMask{dh2, h2, 1.f}, 2,
+                     FinMask{dh1, h1d, make_drop(drop_p, 0).scale}, 2, reinterpret_cast<hipStream_t>(stream));
   MST_HIP_CHECK(hipGetLastError());
   return MST_OK;
 }
@@ -584,32 +653,23 @@ int mst_film_backward(const mst_film_dims* dm, const mst_film_weights* w, const 
 // fixed-order sum, as in mst_film_backward.  Workspace: h1, h2, dh2, dh1 and the partial sums.
 size_t mst_film_input_grad_workspace_bytes(const mst_film_dims* d, int B) {
   if (!d || B <= 0) return 0;
-  return ((size_t)4 * B * d->hidden + (size_t)kSplitFilmOut * B * std::max(d->hidden, d->feature_dim)) * sizeof(float);
+  return mlp_buf(B, d->hidden, 4, kSplitFilmOut, std::max(d->hidden, d->feature_dim)).total * sizeof(float);
 }
 
 int mst_film_input_grad(const mst_film_dims* dm, const mst_film_weights* w, const float* feats, int B, const float* dfilm, float* dfeats,
                         void* workspace, size_t workspace_bytes, void* stream) {
-  MST_REQUIRE(dm && w && feats && dfilm && dfeats && workspace && B > 0, "mst_film_input_grad: NULL / bad argument");
-  MST_REQUIRE(w->mlp0_w && w->mlp0_b && w->mlp3_w && w->mlp3_b && w->head_w && w->head_b, "mst_film_input_grad: NULL weight");
-  const int Fd = dm->feature_dim, H = dm->hidden, O = dm->out_dim;
-  MST_REQUIRE(Fd >= 1 && Fd <= 2048 && H >= 1 && H <= 2048 && O >= 1, "mst_film_input_grad: dims out of range (feature_dim=%d hidden=%d out_dim=%d; limits 2048, 2048)", Fd, H, O);
-  const size_t need = mst_film_input_grad_workspace_bytes(dm, B);
-  if (workspace_bytes < need) return mst::fail(MST_ENOMEM, "mst_film_input_grad: workspace %zu B < required %zu B", workspace_bytes, need);
+  MST_REQUIRE(dm && w && feats && dfilm && dfeats && workspace, "mst_film_input_grad: NULL argument");
+  const Mlp n = mlp_net("mst_film_input_grad", dm, w, B);
+  if (const int rc = mlp_check(n, kFilmLimits, nullptr, 0.f, 0.f)) return rc;
+  const MlpBuf Wk = mlp_buf(B, n.H, 4, kSplitFilmOut, std::max(n.H, n.I));
+  if (const int rc = mlp_room(n.fn, "workspace", workspace_bytes, Wk)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  float* h1 = static_cast<float*>(workspace);
-  float* h2 = h1 + (size_t)B * H;
-  float* dh2 = h2 + (size_t)B * H;
-  float* dh1 = dh2 + (size_t)B * H;
-  float* part = dh1 + (size_t)B * H;
-  auto linear = [&](const float* X, const float* W, const float* bias, float* out, int N, int K) {   // out = ReLU(X W^T + b)
-    hipLaunchKernelGGL((gemm_kernel<false, false, RowMajA, RowMajT, LinEpi>), dim3((N + 63) / 64, (B + 63) / 64, 1), dim3(256), 0, st, B, N, K, 1,
-                       round_up(K, kKC), RowMajA{X, K}, RowMajT{W, K}, LinEpi{out, bias, N, 1, make_drop(0.f, 0)});
-  };
-  linear(feats, w->mlp0_w, w->mlp0_b, h1, H, Fd);
-  linear(h1, w->mlp3_w, w->mlp3_b, h2, H, H);
-  gemm_split<false, true, true>(B, H, O, kSplitFilmOut, RowMajA{dfilm, O}, RowMajB{w->head_w, H}, part, FinMask{dh2, h2, 1.f}, st);
-  gemm_split<false, true>(B, H, H, 2, RowMajA{dh2, H}, RowMajB{w->mlp3_w, H}, part, FinMask{dh1, h1, 1.f}, st);
-  gemm_split<false, true>(B, Fd, H, 2, RowMajA{dh1, H}, RowMajB{w->mlp0_w, Fd}, part, FinStore{dfeats}, st);
+  float *ws = static_cast<float*>(workspace), *h1 = ws + Wk.at(0), *h2 = ws + Wk.at(1), *dh2 = ws + Wk.at(2), *dh1 = ws + Wk.at(3);
+  const Drop d0 = make_drop(0.f, 0);
+  linear(feats, n.I, n.w[0], n.H, B, 0, nullptr, LinEpi{h1, n.b[0], n.H, 1, d0}, st);
+  linear(h1, n.H, n.w[1], n.H, B, 0, nullptr, LinEpi{h2, n.b[1], n.H, 1, d0}, st);
+  mlp_backward<true>(n, feats, h1, h2, dfilm, nullptr, dfeats, dh2, dh1, ws + Wk.part, kSplitFilmOut, FinMask{dh2, h2, 1.f}, 2, FinMask{dh1, h1, 1.f},
+                     2, st);
   MST_HIP_CHECK(hipGetLastError());
   return MST_OK;
 }
@@ -624,8 +684,12 @@ int mst_film_input_grad(const mst_film_dims* dm, const mst_film_weights* w, cons
 // kernel; the input of this network is the embedding, so the backward also returns dx.
 // ------------------------------------------------------------------------------------------
 namespace {
-constexpr int kSplitDisc = kSplitFilm;
 constexpr int kDiscMaxDim = 2048, kDiscMaxRows = 1 << 20;
+const MlpLimits kDiscLimits{"in_dim", "hidden", kDiscMaxDim, kDiscMaxDim, kDiscMaxDim, kDiscMaxRows};
+// save buffer: the two dropped activations, then the forward's split-K partial sums; backward scratch: dh2, dh1, partial sums
+// (the discriminator's and the generator's: every product of both is cut into kSplitFilm slices)
+MlpBuf split_save(int B, int H, int O) { return mlp_buf(B, H, 2, kSplitFilm, std::max(H, O)); }
+MlpBuf split_work(int B, int I, int H) { return mlp_buf(B, H, 2, kSplitFilm, std::max(H, I)); }
 struct FinLin {   // out[m][n] = Dropout(act(sum + bias[n])), element index m * N + n
   float* out; const float* bias; int N, relu; Drop d;
   __device__ void operator()(long long i, float v) const {
@@ -634,28 +698,6 @@ struct FinLin {   // out[m][n] = Dropout(act(sum + bias[n])), element index m * 
     out[i] = drop_apply(d, (size_t)i, x);
   }
 };
-struct DiscSave {   // offsets (floats): the two dropped activations, then the forward's split-K partial sums
-  size_t h1, h2, part, total;
-};
-DiscSave disc_save(int B, int H, int O) {
-  DiscSave s{};
-  s.h1 = 0, s.h2 = (size_t)B * H, s.part = 2 * (size_t)B * H;
-  s.total = s.part + (size_t)kSplitDisc * B * std::max(H, O);
-  return s;
-}
-struct DiscWork {   // backward scratch: dh2, dh1, split-K partial sums
-  size_t dh2, dh1, part, total;
-};
-DiscWork disc_work(int B, int I, int H) {
-  DiscWork s{};
-  s.dh2 = 0, s.dh1 = (size_t)B * H, s.part = 2 * (size_t)B * H;
-  s.total = s.part + (size_t)kSplitDisc * B * std::max(H, I);
-  return s;
-}
-bool disc_dims_ok(const mst_disc_dims* d) {
-  return d->in_dim >= 1 && d->in_dim <= kDiscMaxDim && d->hidden >= 1 && d->hidden <= kDiscMaxDim && d->out_dim >= 1 &&
-         d->out_dim <= kDiscMaxDim;
-}
 
 // The forward without a save buffer (no backward will follow, nowhere to keep the activations): block = one row, the three
 // layers back to back with x, h1 and h2 in LDS; a wave per output unit, lanes over the input units (consecutive addresses of
@@ -748,36 +790,30 @@ __global__ __launch_bounds__(256) void cosdist_bwd_kernel(const float* __restric
 extern "C" {
 
 size_t mst_disc_save_bytes(const mst_disc_dims* d, int B) {
-  if (!d || B <= 0 || B > kDiscMaxRows || !disc_dims_ok(d)) return 0;
-  return disc_save(B, d->hidden, d->out_dim).total * sizeof(float);
+  if (!mlp_in_limits(kDiscLimits, d, B)) return 0;
+  return split_save(B, d->hidden, d->out_dim).total * sizeof(float);
 }
 size_t mst_disc_backward_workspace_bytes(const mst_disc_dims* d, int B) {
-  if (!d || B <= 0 || B > kDiscMaxRows || !disc_dims_ok(d)) return 0;
-  return disc_work(B, d->in_dim, d->hidden).total * sizeof(float);
+  if (!mlp_in_limits(kDiscLimits, d, B)) return 0;
+  return split_work(B, d->in_dim, d->hidden).total * sizeof(float);
 }
 
 int mst_disc_forward(const mst_disc_dims* dm, const mst_disc_weights* w, const float* x, int B, float drop_p, uint64_t seed1,
                      uint64_t seed2, float* pred, void* save, size_t save_bytes, void* stream) {
   MST_REQUIRE(dm && w && x && pred, "mst_disc_forward: NULL argument");
-  MST_REQUIRE(w->w0 && w->b0 && w->w3 && w->b3 && w->w6 && w->b6, "mst_disc_forward: NULL weight");
-  MST_REQUIRE(disc_dims_ok(dm), "mst_disc_forward: dims out of range (in_dim=%d hidden=%d out_dim=%d; each must be in 1..%d)", dm->in_dim,
-              dm->hidden, dm->out_dim, kDiscMaxDim);
-  MST_REQUIRE(B >= 1 && B <= kDiscMaxRows, "mst_disc_forward: B=%d rows, must be in 1..%d", B, kDiscMaxRows);
-  MST_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "mst_disc_forward: dropout p must be in [0, 1)");
-  const int I = dm->in_dim, H = dm->hidden, O = dm->out_dim;
+  const Mlp n = mlp_net("mst_disc_forward", dm, w, B);
+  if (const int rc = mlp_check(n, kDiscLimits, nullptr, drop_p, drop_p)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const Drop d1 = make_drop(drop_p, seed1), d2 = make_drop(drop_p, seed2), d0 = make_drop(0.f, 0);
   if (!save) {
-    hipLaunchKernelGGL(disc_row_kernel, dim3(B), dim3(256), 0, st, x, w->w0, w->b0, w->w3, w->b3, w->w6, w->b6, pred, I, H, O, d1, d2);
+    hipLaunchKernelGGL(disc_row_kernel, dim3(B), dim3(256), 0, st, x, n.w[0], n.b[0], n.w[1], n.b[1], n.w[2], n.b[2], pred, n.I, n.H, n.O, d1, d2);
     MST_HIP_CHECK(hipGetLastError());
     return MST_OK;
   }
-  const DiscSave S = disc_save(B, H, O);
-  if (save_bytes < S.total * sizeof(float)) return mst::fail(MST_ENOMEM, "mst_disc_forward: save buffer %zu B < %zu B", save_bytes, S.total * sizeof(float));
-  float* sv = static_cast<float*>(save);
-  gemm_split<false, false>(B, H, I, kSplitDisc, RowMajA{x, I}, RowMajT{w->w0, I}, sv + S.part, FinLin{sv + S.h1, w->b0, H, 1, d1}, st);
-  gemm_split<false, false>(B, H, H, kSplitDisc, RowMajA{sv + S.h1, H}, RowMajT{w->w3, H}, sv + S.part, FinLin{sv + S.h2, w->b3, H, 1, d2}, st);
-  gemm_split<false, false>(B, O, H, kSplitDisc, RowMajA{sv + S.h2, H}, RowMajT{w->w6, H}, sv + S.part, FinLin{pred, w->b6, O, 0, d0}, st);
+  const MlpBuf S = split_save(B, n.H, n.O);
+  if (const int rc = mlp_room(n.fn, "save buffer", save_bytes, S)) return rc;
+  float *sv = static_cast<float*>(save), *h1 = sv + S.at(0), *h2 = sv + S.at(1);
+  mlp_forward(n, x, h1, h2, kSplitFilm, sv + S.part, FinLin{h1, n.b[0], n.H, 1, d1}, FinLin{h2, n.b[1], n.H, 1, d2}, FinLin{pred, n.b[2], n.O, 0, d0}, st);
   MST_HIP_CHECK(hipGetLastError());
   return MST_OK;
 }
@@ -787,34 +823,16 @@ int mst_disc_backward(const mst_disc_dims* dm, const mst_disc_weights* w, const 
                       size_t workspace_bytes, void* stream) {
   (void)seed1, (void)seed2;   // the survivors of a Dropout behind a ReLU are exactly the positive entries of the saved activation
   MST_REQUIRE(dm && w && x && dpred && save && g && workspace, "mst_disc_backward: NULL argument");
-  MST_REQUIRE(w->w0 && w->b0 && w->w3 && w->b3 && w->w6 && w->b6, "mst_disc_backward: NULL weight");
-  MST_REQUIRE(g->w0 && g->b0 && g->w3 && g->b3 && g->w6 && g->b6, "mst_disc_backward: NULL gradient pointer");
-  MST_REQUIRE(disc_dims_ok(dm), "mst_disc_backward: dims out of range (in_dim=%d hidden=%d out_dim=%d; each must be in 1..%d)", dm->in_dim,
-              dm->hidden, dm->out_dim, kDiscMaxDim);
-  MST_REQUIRE(B >= 1 && B <= kDiscMaxRows, "mst_disc_backward: B=%d rows, must be in 1..%d", B, kDiscMaxRows);
-  MST_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "mst_disc_backward: dropout p must be in [0, 1)");
-  const int I = dm->in_dim, H = dm->hidden, O = dm->out_dim;
-  const DiscSave S = disc_save(B, H, O);
-  const DiscWork Wk = disc_work(B, I, H);
-  if (workspace_bytes < Wk.total * sizeof(float)) return mst::fail(MST_ENOMEM, "mst_disc_backward: workspace %zu B < %zu B", workspace_bytes, Wk.total * sizeof(float));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const float* sv = static_cast<const float*>(save);
-  const float *h1 = sv + S.h1, *h2 = sv + S.h2;
-  float* ws = static_cast<float*>(workspace);
-  float *dh2 = ws + Wk.dh2, *dh1 = ws + Wk.dh1, *part = ws + Wk.part;
-  const float gscale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-  const dim3 blk(256);
-  auto wgrad = [&](const float* dy, int N, const float* in, int K, float* dw, float* db) {   // db = colsum(dy), dw = dy^T in
-    hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64), blk, 0, st, dy, db, B, N);
-    hipLaunchKernelGGL((gemm_kernel<true, true, ColMajA, RowMajB, EpiStore>), dim3((K + 63) / 64, (N + 63) / 64, 1), blk, 0, st, N, K, B, 1,
-                       round_up(B, kKC), ColMajA{dy, N}, RowMajB{in, K}, EpiStore{dw, K});
-  };
-  wgrad(dpred, O, h2, H, g->w6, g->b6);
-  gemm_split<false, true>(B, H, O, kSplitDisc, RowMajA{dpred, O}, RowMajB{w->w6, H}, part, FinMask{dh2, h2, gscale}, st);
-  wgrad(dh2, H, h1, H, g->w3, g->b3);
-  gemm_split<false, true>(B, H, H, kSplitDisc, RowMajA{dh2, H}, RowMajB{w->w3, H}, part, FinMask{dh1, h1, gscale}, st);
-  wgrad(dh1, H, x, I, g->w0, g->b0);
-  if (dx) gemm_split<false, true>(B, I, H, kSplitDisc, RowMajA{dh1, H}, RowMajB{w->w0, I}, part, FinStore{dx}, st);
+  const Mlp n = mlp_net("mst_disc_backward", dm, w, B);
+  const MlpGrads G = mlp_grads(g);
+  if (const int rc = mlp_check(n, kDiscLimits, &G, drop_p, drop_p)) return rc;
+  const MlpBuf S = split_save(B, n.H, n.O), Wk = split_work(B, n.I, n.H);
+  if (const int rc = mlp_room(n.fn, "workspace", workspace_bytes, Wk)) return rc;
+  const float *sv = static_cast<const float*>(save), *h1 = sv + S.at(0), *h2 = sv + S.at(1);
+  float *ws = static_cast<float*>(workspace), *dh2 = ws + Wk.at(0), *dh1 = ws + Wk.at(1);
+  const float gscale = make_drop(drop_p, 0).scale;
+  mlp_backward<false>(n, x, h1, h2, dpred, &G, dx, dh2, dh1, ws + Wk.part, kSplitFilm, FinMask{dh2, h2, gscale}, kSplitFilm, FinMask{dh1, h1, gscale},
+                      kSplitFilm, reinterpret_cast<hipStream_t>(stream));
   MST_HIP_CHECK(hipGetLastError());
   return MST_OK;
 }
@@ -851,8 +869,7 @@ int mst_cosdist_backward(const float* pred, const float* target, int K, int D, c
 // reads the saved activation only for its sign (h > 0 -> 1, else the slope: PyTorch's branch for x <= 0).
 // ------------------------------------------------------------------------------------------
 namespace {
-constexpr int kSplitGen = kSplitFilm;
-constexpr int kGenMaxEmbed = 4096, kGenMaxHidden = 2048, kGenMaxOut = 8192, kGenMaxRows = 65535;
+const MlpLimits kGenLimits{"embed_dim", "mlp_hidden", 4096, 2048, 8192, 65535};
 struct FinLeaky {   // out[m][n] = Dropout(LeakyReLU(sum + bias[n])), element index m * N + n
   float* out; const float* bias; int N; float slope; Drop d;
   __device__ void operator()(long long i, float v) const {
@@ -869,35 +886,10 @@ struct FinLeakyMask {   // d pre-activation = keep(seed, i) ? sum * scale * (h >
     out[i] = h[i] > 0.f ? g : g * slope;
   }
 };
-struct GenSave {   // offsets (floats): the two dropped activations, then the forward's split-K partial sums
-  size_t h1, h2, part, total;
-};
-GenSave gen_save(int B, int H, int O) {
-  GenSave s{};
-  s.h1 = 0, s.h2 = (size_t)B * H, s.part = 2 * (size_t)B * H;
-  s.total = s.part + (size_t)kSplitGen * B * std::max(H, O);
-  return s;
-}
-struct GenWork {   // backward scratch: dh2, dh1, split-K partial sums
-  size_t dh2, dh1, part, total;
-};
-GenWork gen_work(int B, int I, int H) {
-  GenWork s{};
-  s.dh2 = 0, s.dh1 = (size_t)B * H, s.part = 2 * (size_t)B * H;
-  s.total = s.part + (size_t)kSplitGen * B * std::max(H, I);
-  return s;
-}
-bool gen_dims_ok(const mst_tcn_film_train_dims* d) {
-  return d->embed_dim >= 1 && d->embed_dim <= kGenMaxEmbed && d->mlp_hidden >= 1 && d->mlp_hidden <= kGenMaxHidden && d->out_dim >= 1 &&
-         d->out_dim <= kGenMaxOut;
-}
-// the limits both entry points share, refused under the caller's name `fn`
-int gen_check(const char* fn, const mst_tcn_film_train_dims* dm, int B, float p1, float p2, float slope) {
-  MST_REQUIRE(gen_dims_ok(dm), "%s: dims out of range (embed_dim=%d in 1..%d, mlp_hidden=%d in 1..%d, out_dim=%d in 1..%d)", fn,
-              dm->embed_dim, kGenMaxEmbed, dm->mlp_hidden, kGenMaxHidden, dm->out_dim, kGenMaxOut);
-  MST_REQUIRE(B >= 1 && B <= kGenMaxRows, "%s: B=%d rows, must be in 1..%d", fn, B, kGenMaxRows);
-  MST_REQUIRE(p1 >= 0.f && p1 < 1.f && p2 >= 0.f && p2 < 1.f, "%s: dropout p must be in [0, 1)", fn);
-  MST_REQUIRE(slope >= 0.f && slope <= 1.f, "%s: LeakyReLU slope must be in [0, 1]", fn);
+// what both entry points refuse: mlp_check and the slope
+int gen_check(const Mlp& n, const MlpGrads* g, float p1, float p2, float slope) {
+  if (const int rc = mlp_check(n, kGenLimits, g, p1, p2)) return rc;
+  MST_REQUIRE(slope >= 0.f && slope <= 1.f, "%s: LeakyReLU slope must be in [0, 1]", n.fn);
   return MST_OK;
 }
 }  // namespace
@@ -905,30 +897,26 @@ int gen_check(const char* fn, const mst_tcn_film_train_dims* dm, int B, float p1
 extern "C" {
 
 size_t mst_tcn_film_train_save_bytes(const mst_tcn_film_train_dims* d, int B) {
-  if (!d || B <= 0 || B > kGenMaxRows || !gen_dims_ok(d)) return 0;
-  return gen_save(B, d->mlp_hidden, d->out_dim).total * sizeof(float);
+  if (!mlp_in_limits(kGenLimits, d, B)) return 0;
+  return split_save(B, d->mlp_hidden, d->out_dim).total * sizeof(float);
 }
 size_t mst_tcn_film_train_backward_workspace_bytes(const mst_tcn_film_train_dims* d, int B) {
-  if (!d || B <= 0 || B > kGenMaxRows || !gen_dims_ok(d)) return 0;
-  return gen_work(B, d->embed_dim, d->mlp_hidden).total * sizeof(float);
+  if (!mlp_in_limits(kGenLimits, d, B)) return 0;
+  return split_work(B, d->embed_dim, d->mlp_hidden).total * sizeof(float);
 }
 
 int mst_tcn_film_forward_train(const mst_tcn_film_train_dims* dm, const mst_tcn_film_weights* w, const float* emb, int B, float slope,
                                float drop_p1, uint64_t seed1, float drop_p2, uint64_t seed2, float* film, void* save, size_t save_bytes,
                                void* stream) {
   MST_REQUIRE(dm && w && emb && film && save, "mst_tcn_film_forward_train: NULL argument");
-  MST_REQUIRE(w->mlp0_w && w->mlp0_b && w->mlp3_w && w->mlp3_b && w->mlp6_w && w->mlp6_b, "mst_tcn_film_forward_train: NULL weight");
-  if (const int rc = gen_check("mst_tcn_film_forward_train", dm, B, drop_p1, drop_p2, slope)) return rc;
-  const int I = dm->embed_dim, H = dm->mlp_hidden, O = dm->out_dim;
-  const GenSave S = gen_save(B, H, O);
-  if (save_bytes < S.total * sizeof(float))
-    return mst::fail(MST_ENOMEM, "mst_tcn_film_forward_train: save buffer %zu B < %zu B", save_bytes, S.total * sizeof(float));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  float* sv = static_cast<float*>(save);
-  const Drop d1 = make_drop(drop_p1, seed1), d2 = make_drop(drop_p2, seed2);
-  gemm_split<false, false>(B, H, I, kSplitGen, RowMajA{emb, I}, RowMajT{w->mlp0_w, I}, sv + S.part, FinLeaky{sv + S.h1, w->mlp0_b, H, slope, d1}, st);
-  gemm_split<false, false>(B, H, H, kSplitGen, RowMajA{sv + S.h1, H}, RowMajT{w->mlp3_w, H}, sv + S.part, FinLeaky{sv + S.h2, w->mlp3_b, H, slope, d2}, st);
-  gemm_split<false, false>(B, O, H, kSplitGen, RowMajA{sv + S.h2, H}, RowMajT{w->mlp6_w, H}, sv + S.part, FinLin{film, w->mlp6_b, O, 0, make_drop(0.f, 0)}, st);
+  const Mlp n = mlp_net("mst_tcn_film_forward_train", dm, w, B);
+  if (const int rc = gen_check(n, nullptr, drop_p1, drop_p2, slope)) return rc;
+  const MlpBuf S = split_save(B, n.H, n.O);
+  if (const int rc = mlp_room(n.fn, "save buffer", save_bytes, S)) return rc;
+  float *sv = static_cast<float*>(save), *h1 = sv + S.at(0), *h2 = sv + S.at(1);
+  mlp_forward(n, emb, h1, h2, kSplitFilm, sv + S.part, FinLeaky{h1, n.b[0], n.H, slope, make_drop(drop_p1, seed1)},
+              FinLeaky{h2, n.b[1], n.H, slope, make_drop(drop_p2, seed2)}, FinLin{film, n.b[2], n.O, 0, make_drop(0.f, 0)},
+              reinterpret_cast<hipStream_t>(stream));
   MST_HIP_CHECK(hipGetLastError());
   return MST_OK;
 }
@@ -937,32 +925,15 @@ int mst_tcn_film_backward(const mst_tcn_film_train_dims* dm, const mst_tcn_film_
                           float drop_p1, uint64_t seed1, float drop_p2, uint64_t seed2, const float* dfilm, const void* save,
                           const mst_tcn_film_grads* g, float* demb, void* workspace, size_t workspace_bytes, void* stream) {
   MST_REQUIRE(dm && w && emb && dfilm && save && g && workspace, "mst_tcn_film_backward: NULL argument");
-  MST_REQUIRE(w->mlp0_w && w->mlp0_b && w->mlp3_w && w->mlp3_b && w->mlp6_w && w->mlp6_b, "mst_tcn_film_backward: NULL weight");
-  MST_REQUIRE(g->mlp0_w && g->mlp0_b && g->mlp3_w && g->mlp3_b && g->mlp6_w && g->mlp6_b, "mst_tcn_film_backward: NULL gradient pointer");
-  if (const int rc = gen_check("mst_tcn_film_backward", dm, B, drop_p1, drop_p2, slope)) return rc;
-  const int I = dm->embed_dim, H = dm->mlp_hidden, O = dm->out_dim;
-  const GenSave S = gen_save(B, H, O);
-  const GenWork Wk = gen_work(B, I, H);
-  if (workspace_bytes < Wk.total * sizeof(float))
-    return mst::fail(MST_ENOMEM, "mst_tcn_film_backward: workspace %zu B < %zu B", workspace_bytes, Wk.total * sizeof(float));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const float* sv = static_cast<const float*>(save);
-  const float *h1 = sv + S.h1, *h2 = sv + S.h2;
-  float* ws = static_cast<float*>(workspace);
-  float *dh2 = ws + Wk.dh2, *dh1 = ws + Wk.dh1, *part = ws + Wk.part;
-  const Drop d1 = make_drop(drop_p1, seed1), d2 = make_drop(drop_p2, seed2);
-  const dim3 blk(256);
-  auto wgrad = [&](const float* dy, int N, const float* in, int K, float* dw, float* db) {   // db = colsum(dy), dw = dy^T in
-    hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64), blk, 0, st, dy, db, B, N);
-    hipLaunchKernelGGL((gemm_kernel<true, true, ColMajA, RowMajB, EpiStore>), dim3((K + 63) / 64, (N + 63) / 64, 1), blk, 0, st, N, K, B, 1,
-                       round_up(B, kKC), ColMajA{dy, N}, RowMajB{in, K}, EpiStore{dw, K});
-  };
-  wgrad(dfilm, O, h2, H, g->mlp6_w, g->mlp6_b);
-  gemm_split<false, true>(B, H, O, kSplitGen, RowMajA{dfilm, O}, RowMajB{w->mlp6_w, H}, part, FinLeakyMask{dh2, h2, slope, d2}, st);
-  wgrad(dh2, H, h1, H, g->mlp3_w, g->mlp3_b);
-  gemm_split<false, true>(B, H, H, kSplitGen, RowMajA{dh2, H}, RowMajB{w->mlp3_w, H}, part, FinLeakyMask{dh1, h1, slope, d1}, st);
-  wgrad(dh1, H, emb, I, g->mlp0_w, g->mlp0_b);
-  if (demb) gemm_split<false, true>(B, I, H, kSplitGen, RowMajA{dh1, H}, RowMajB{w->mlp0_w, I}, part, FinStore{demb}, st);
+  const Mlp n = mlp_net("mst_tcn_film_backward", dm, w, B);
+  const MlpGrads G = mlp_grads(g);
+  if (const int rc = gen_check(n, &G, drop_p1, drop_p2, slope)) return rc;
+  const MlpBuf S = split_save(B, n.H, n.O), Wk = split_work(B, n.I, n.H);
+  if (const int rc = mlp_room(n.fn, "workspace", workspace_bytes, Wk)) return rc;
+  const float *sv = static_cast<const float*>(save), *h1 = sv + S.at(0), *h2 = sv + S.at(1);
+  float *ws = static_cast<float*>(workspace), *dh2 = ws + Wk.at(0), *dh1 = ws + Wk.at(1);
+  mlp_backward<false>(n, emb, h1, h2, dfilm, &G, demb, dh2, dh1, ws + Wk.part, kSplitFilm, FinLeakyMask{dh2, h2, slope, make_drop(drop_p2, seed2)},
+                      kSplitFilm, FinLeakyMask{dh1, h1, slope, make_drop(drop_p1, seed1)}, kSplitFilm, reinterpret_cast<hipStream_t>(stream));
   MST_HIP_CHECK(hipGetLastError());
   return MST_OK;
 }

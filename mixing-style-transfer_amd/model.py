@@ -32,6 +32,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from ._mlp import DISC, FILM, _HipMLP, _seed64, mlp_buffer, mlp_call, mlp_dims, mlp_ptrs
 from .mixing_utils import (LOGMEL_BAND_MAX, STEMS, LogMel, MelFeatPlan, detailed_bins_for_feature_dim, hann_window, is_deferred,
                            feature_grad_refusal, mel_band_table, mel_bin_ranges, melfeat_backward, melscale_fbanks_htk,
                            stems_to_tensor)
@@ -952,21 +953,12 @@ class _HipFrozenTrunk(torch.autograd.Function):
 def _film_input_grad(feats, dfilm, film_w):
     """`mst_film_input_grad`: d film (B, O) -> d feats (B, Fd) through the eval-mode FiLM MLP (weights: mlp0, mlp3, film_head)."""
     B = feats.shape[0]
-    dims = _lib.FilmDims(film_w[0].shape[1], film_w[0].shape[0], film_w[4].shape[0])
-    L = _lib.lib()
-    work = torch.empty(L.mst_film_input_grad_workspace_bytes(C.byref(dims), B), dtype=torch.uint8, device=feats.device)
+    dims = mlp_dims(FILM, film_w)
+    work = mlp_buffer("mst_film_input_grad_workspace_bytes", dims, B, feats.device)
     out = torch.empty_like(feats)
-    wp = _lib.FilmPtrs(*[t.data_ptr() for t in film_w])
-    with torch.cuda.device(feats.device):
-        _lib.check(L.mst_film_input_grad(C.byref(dims), C.byref(wp), _lib.dptr(feats), B, _lib.dptr(dfilm.contiguous().float()),
-                                         _lib.dptr(out), _lib.dptr(work), work.numel(), _lib.stream_ptr(feats.device)),
-                   "mst_film_input_grad")
+    mlp_call("mst_film_input_grad", feats.device, C.byref(dims), mlp_ptrs(FILM.weights, film_w), feats, B, dfilm.contiguous().float(), out,
+             work, work.numel())
     return out
-
-
-def _seed64():
-    """A 62-bit seed from torch's CPU generator (reproducible under torch.manual_seed; no device work)."""
-    return int(torch.randint(0, 2 ** 62, (1,)).item())
 
 
 class _HipHead(torch.autograd.Function):
@@ -1009,85 +1001,6 @@ class _HipHead(torch.autograd.Function):
                                            _lib.dptr(save), C.byref(gp), _lib.dptr(dx), _lib.dptr(work), work.numel(),
                                            _lib.stream_ptr(x.device)), "mst_head_backward")
         return (dx, None, None) + tuple(grads)
-
-
-class _HipFilmMLP(torch.autograd.Function):
-    """MixingFeatureEncoder's MLP + film_head (src/model.py:410-464) for training, forward and backward in libmst.so
-    (`mst_film_forward_train` / `mst_film_backward`).  The features get no gradient (they are data)."""
-
-    @staticmethod
-    def forward(ctx, feats, p, w0, b0, w3, b3, wh, bh):
-        f = feats.contiguous().float()
-        B = f.shape[0]
-        ws = [t.detach().contiguous().float() for t in (w0, b0, w3, b3, wh, bh)]
-        dims = _lib.FilmDims(ws[0].shape[1], ws[0].shape[0], ws[4].shape[0])
-        L = _lib.lib()
-        seed = _seed64() if p > 0.0 else 0
-        save = torch.empty(L.mst_film_save_bytes(C.byref(dims), B), dtype=torch.uint8, device=f.device)
-        film = torch.empty(B, ws[4].shape[0], device=f.device)
-        wp = _lib.FilmPtrs(*[t.data_ptr() for t in ws])
-        with torch.cuda.device(f.device):
-            _lib.check(L.mst_film_forward_train(C.byref(dims), C.byref(wp), _lib.dptr(f), B, float(p), seed, _lib.dptr(film), _lib.dptr(save),
-                                                save.numel(), _lib.stream_ptr(f.device)), "mst_film_forward_train")
-        ctx.cfg = (dims, float(p))
-        ctx.save_for_backward(f, save, *ws)
-        return film
-
-    @staticmethod
-    def backward(ctx, dfilm):
-        f, save, *ws = ctx.saved_tensors
-        dims, p = ctx.cfg
-        B = f.shape[0]
-        L = _lib.lib()
-        grads = [torch.empty_like(t) for t in ws]
-        work = torch.empty(L.mst_film_backward_workspace_bytes(C.byref(dims), B), dtype=torch.uint8, device=f.device)
-        df = dfilm.contiguous().float()
-        wp, gp = _lib.FilmPtrs(*[t.data_ptr() for t in ws]), _lib.FilmPtrs(*[t.data_ptr() for t in grads])
-        with torch.cuda.device(f.device):
-            _lib.check(L.mst_film_backward(C.byref(dims), C.byref(wp), _lib.dptr(f), B, p, _lib.dptr(df), _lib.dptr(save), C.byref(gp),
-                                           _lib.dptr(work), work.numel(), _lib.stream_ptr(f.device)), "mst_film_backward")
-        return (None, None) + tuple(grads)
-
-
-class _HipDiscriminator(torch.autograd.Function):
-    """SongIdentityDiscriminator's network (src/model.py:545-587) for training and evaluation, forward and backward in libmst.so
-    (`mst_disc_forward` / `mst_disc_backward`, csrc/head.hip).  Unlike the FiLM MLP's features, the input is the embedding and
-    gets its gradient -- that gradient, reversed, is what the adversarial branch trains the encoder with."""
-
-    @staticmethod
-    def forward(ctx, x, p, w0, b0, w3, b3, w6, b6):
-        f = x.detach().contiguous().float()
-        B = f.shape[0]
-        ws = [t.detach().contiguous().float() for t in (w0, b0, w3, b3, w6, b6)]
-        dims = _lib.DiscDims(ws[0].shape[1], ws[0].shape[0], ws[4].shape[0])
-        L = _lib.lib()
-        seeds = (_seed64(), _seed64()) if p > 0.0 else (0, 0)
-        save = torch.empty(L.mst_disc_save_bytes(C.byref(dims), B), dtype=torch.uint8, device=f.device)
-        pred = torch.empty(B, ws[4].shape[0], device=f.device)
-        wp = _lib.DiscPtrs(*[t.data_ptr() for t in ws])
-        with torch.cuda.device(f.device):
-            _lib.check(L.mst_disc_forward(C.byref(dims), C.byref(wp), _lib.dptr(f), B, float(p), seeds[0], seeds[1], _lib.dptr(pred),
-                                          _lib.dptr(save), save.numel(), _lib.stream_ptr(f.device)), "mst_disc_forward")
-        ctx.cfg = (dims, float(p), seeds)
-        ctx.save_for_backward(f, save, *ws)
-        return pred
-
-    @staticmethod
-    def backward(ctx, dpred):
-        f, save, *ws = ctx.saved_tensors
-        dims, p, seeds = ctx.cfg
-        B = f.shape[0]
-        L = _lib.lib()
-        grads = [torch.empty_like(t) for t in ws]
-        dx = torch.empty_like(f) if ctx.needs_input_grad[0] else None   # (a detached input: the discriminator trains alone)
-        work = torch.empty(L.mst_disc_backward_workspace_bytes(C.byref(dims), B), dtype=torch.uint8, device=f.device)
-        dp = dpred.contiguous().float()
-        wp, gp = _lib.DiscPtrs(*[t.data_ptr() for t in ws]), _lib.DiscPtrs(*[t.data_ptr() for t in grads])
-        with torch.cuda.device(f.device):
-            _lib.check(L.mst_disc_backward(C.byref(dims), C.byref(wp), _lib.dptr(f), B, p, seeds[0], seeds[1], _lib.dptr(dp),
-                                           _lib.dptr(save), C.byref(gp), _lib.dptr(dx), _lib.dptr(work), work.numel(),
-                                           _lib.stream_ptr(f.device)), "mst_disc_backward")
-        return (dx, None) + tuple(grads)
 
 
 class MixingStyleEncoder(nn.Module):
@@ -1226,8 +1139,8 @@ class MixingStyleEncoder(nn.Module):
         hip_small = self._small_nets_in_hip(mixing_features, (logmel.frames if isinstance(logmel, LogMel) else logmel.shape[-1]) // 20)
         if hip_small:   # FiLM MLP forward / backward in libmst.so (csrc/head.hip)
             mlp = fe.feature_mlp
-            flat = _HipFilmMLP.apply(mixing_features, float(mlp[2].p) if self.training else 0.0, mlp[0].weight, mlp[0].bias,
-                                     mlp[3].weight, mlp[3].bias, fe.film_head.weight, fe.film_head.bias)
+            flat = _HipMLP.apply(FILM, mixing_features, None, float(mlp[2].p) if self.training else 0.0, 0.0, 0.0, mlp[0].weight, mlp[0].bias,
+                                 mlp[3].weight, mlp[3].bias, fe.film_head.weight, fe.film_head.bias)
         else:
             flat = fe.film_head(fe.feature_mlp(mixing_features))
         p = cn[0].dropout1.p if self.training else 0.0
@@ -1496,7 +1409,7 @@ class SongIdentityDiscriminator(nn.Module):
     and state_dict keys (`network.0.weight` ... `network.6.bias`): a reference checkpoint's `discriminator_state_dict` loads
     with strict=True.
 
-    `backend`: "hip" (default) = forward and backward in libmst.so (see _HipDiscriminator) for fp32 CUDA input; a call it cannot
+    `backend`: "hip" (default) = forward and backward in libmst.so (see _mlp._HipMLP) for fp32 CUDA input; a call it cannot
     take raises RuntimeError naming the reason.  "torch" = explicit opt-in, `self.network` on PyTorch ops (any device, dtype).
     Inside `torch.autocast` the module runs `self.network` (as the FiLM MLP and the pooling head do: src/train.py:246-296 calls
     it there with half-precision embeddings)."""
@@ -1539,6 +1452,7 @@ class SongIdentityDiscriminator(nn.Module):
         if why:
             raise RuntimeError("SongIdentityDiscriminator: " + why + "; backend='torch' runs the same network on PyTorch ops")
         net = self.network
-        out = _HipDiscriminator.apply(x.reshape(-1, x.shape[-1]), float(net[2].p) if self.training else 0.0, net[0].weight, net[0].bias,
-                                      net[3].weight, net[3].bias, net[6].weight, net[6].bias)
+        p = float(net[2].p) if self.training else 0.0
+        out = _HipMLP.apply(DISC, x.reshape(-1, x.shape[-1]), None, p, p, 0.0, net[0].weight, net[0].bias, net[3].weight, net[3].bias,
+                            net[6].weight, net[6].bias)
         return out.view(*x.shape[:-1], out.shape[-1])

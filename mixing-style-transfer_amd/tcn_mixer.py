@@ -35,7 +35,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .model import _seed64
+from ._mlp import TCN_FILM, _HipMLP
 
 STEM_ORDER = ("vocals", "bass", "drums", "other")
 _BACKENDS = ("hip", "torch")
@@ -187,7 +187,7 @@ class TCNFiLMGenerator(nn.Module):
                 nn.init.zeros_(layer.bias)
         self.backend = "hip"
         # training with backend == "hip": "none" (default) = there is none (train() mode or a needed gradient raises and names
-        # backend="torch"); "hip" = train-mode forward and full backward in libmst.so (_FiLMTrainFn) for a call in train() mode or
+        # backend="torch"); "hip" = train-mode forward and full backward in libmst.so (_mlp._HipMLP) for a call in train() mode or
         # one that needs a gradient -- eval() without gradients stays on the inference handle
         self.train_backend = "none"
         self._hip = None
@@ -218,7 +218,7 @@ class TCNFiLMGenerator(nn.Module):
         if B == 0:
             return torch.empty(0, self.num_blocks, 4, self.hidden_channels, device=emb.device, dtype=torch.float32)
         p1, p2 = (float(self.mlp[i].p) if self.training else 0.0 for i in (2, 5))
-        return _FiLMTrainFn.apply(emb, (self.num_blocks, 4, self.hidden_channels), slopes.pop(), p1, p2, *params)
+        return _HipMLP.apply(TCN_FILM, emb, (self.num_blocks, 4, self.hidden_channels), p1, p2, slopes.pop(), *params)
 
     def _handle(self, device):
         key = _state_key(self)
@@ -267,50 +267,6 @@ class TCNFiLMGenerator(nn.Module):
         params = self.film_tensor(concat_embeddings)
         return [{"gamma1": params[:, i, 0, :], "beta1": params[:, i, 1, :], "gamma2": params[:, i, 2, :],
                  "beta2": params[:, i, 3, :]} for i in range(self.num_blocks)]
-
-
-class _FiLMTrainFn(torch.autograd.Function):
-    """TCNFiLMGenerator's MLP for training, forward and backward in libmst.so (`mst_tcn_film_forward_train` /
-    `mst_tcn_film_backward`, csrc/head.hip): fp32, split-K in a fixed order, Dropout masks re-derived from (seed, element).
-    The kernels read the module's live parameters by pointer; the save buffer belongs to the call."""
-
-    @staticmethod
-    def forward(ctx, emb, shape, slope, p1, p2, *params):
-        x = emb.contiguous()
-        B, dev = x.shape[0], x.device
-        dims = _lib.TcnFilmTrainDims(params[0].shape[1], params[0].shape[0], params[4].shape[0])
-        seeds = (_seed64() if p1 > 0.0 else 0, _seed64() if p2 > 0.0 else 0)
-        L = _lib.lib()
-        nsave = L.mst_tcn_film_train_save_bytes(C.byref(dims), B)
-        save = torch.empty(nsave, dtype=torch.uint8, device=dev)
-        film = torch.empty(B, *shape, device=dev, dtype=torch.float32)
-        wp = _lib.TcnFilmWeights(*[p.data_ptr() for p in params])
-        with torch.cuda.device(dev):
-            _lib.check(L.mst_tcn_film_forward_train(C.byref(dims), C.byref(wp), _lib.dptr(x), B, slope, p1, seeds[0], p2, seeds[1],
-                                                    _lib.dptr(film), _lib.dptr(save), nsave, _lib.stream_ptr(dev)),
-                       "mst_tcn_film_forward_train")
-        ctx.cfg = (dims, slope, p1, p2, seeds)
-        ctx.save_for_backward(x, save, *params)   # (autograd's version check covers the parameters the backward reads again)
-        return film
-
-    @staticmethod
-    def backward(ctx, dfilm):
-        x, save, *params = ctx.saved_tensors
-        dims, slope, p1, p2, seeds = ctx.cfg
-        B, dev = x.shape[0], x.device
-        L = _lib.lib()
-        grads = [torch.empty_like(p) for p in params]
-        demb = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        nws = L.mst_tcn_film_train_backward_workspace_bytes(C.byref(dims), B)
-        work = torch.empty(nws, dtype=torch.uint8, device=dev)
-        df = dfilm.contiguous()
-        wp = _lib.TcnFilmWeights(*[p.data_ptr() for p in params])
-        gp = _lib.TcnFilmGrads(*[g.data_ptr() for g in grads])
-        with torch.cuda.device(dev):
-            _lib.check(L.mst_tcn_film_backward(C.byref(dims), C.byref(wp), _lib.dptr(x), B, slope, p1, seeds[0], p2, seeds[1], _lib.dptr(df),
-                                               _lib.dptr(save), C.byref(gp), _lib.dptr(demb), _lib.dptr(work), nws, _lib.stream_ptr(dev)),
-                       "mst_tcn_film_backward")
-        return (demb, None, None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[5:]))
 
 
 _FILM_KEYS = ("gamma1", "beta1", "gamma2", "beta2")

@@ -117,11 +117,11 @@ def test_head_embedding_of_a_clip_does_not_depend_on_the_batch():
 
 
 def _run_film(f, ws, R, p, seed=5):
-    from mst_amd.model import _HipFilmMLP
+    from mst_amd._mlp import FILM, _HipMLP
     ps = [w.cuda().requires_grad_(True) for w in ws]
     torch.manual_seed(seed)
     s = ch.next_seeds(1)[0] if p > 0 else 0
-    film = _HipFilmMLP.apply(f.cuda(), p, *ps)
+    film = _HipMLP.apply(FILM, f.cuda(), None, p, 0.0, 0.0, *ps)
     (film * R.cuda()).sum().backward()
     return film.detach(), [q.grad for q in ps], s
 

@@ -90,7 +90,8 @@ def test_attention_pooling_head_forward_backward(B, Cc, T, p_in, p_out):
 
 @pytest.mark.parametrize("B,Fd,n_sub,p", [(6, 64, 11, 0.0), (6, 64, 11, 0.2), (3, 180, 24, 0.2)])
 def test_film_mlp_forward_backward(B, Fd, n_sub, p):
-    from mst_amd.model import MixingFeatureEncoder, _HipFilmMLP
+    from mst_amd._mlp import FILM, _HipMLP
+    from mst_amd.model import MixingFeatureEncoder
     torch.manual_seed(7 + B)
     fe = MixingFeatureEncoder(Fd, n_sub).cuda()
     f = torch.randn(B, Fd, device="cuda") * 2.0
@@ -99,7 +100,7 @@ def test_film_mlp_forward_backward(B, Fd, n_sub, p):
     ps = [mlp[0].weight, mlp[0].bias, mlp[3].weight, mlp[3].bias, fe.film_head.weight, fe.film_head.bias]
     torch.manual_seed(5)
     seed = _seeds(1)[0] if p > 0 else 0
-    film = _HipFilmMLP.apply(f, p, *ps)
+    film = _HipMLP.apply(FILM, f, None, p, 0.0, 0.0, *ps)
     (film * R).sum().backward()
     got = [q.grad.clone() for q in ps]
     fe64 = MixingFeatureEncoder(Fd, n_sub).cuda().double()
