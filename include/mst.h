@@ -674,7 +674,8 @@ int mst_tcn_film_forward(const mst_tcn_film* gen, const float* emb, int B, float
  * mst_tcn_forward), a handle in MST_TCN_F16X3 mode, B outside 1..65535, max_block < 1 or so large that a ring reaches
  * 2^31 elements, N outside 1..max_block, t0 < 0, film not matching use_film; MST_ENOMEM for a state or workspace smaller
  * than the size queries say.  After mst_tcn_update_params the state's folded table is stale: reset before the next push.
- * FiLM is fixed per reset.  Not built: non-causal streaming with a fixed latency, f16x3 streaming, gradients.
+ * FiLM is fixed per reset.  A non-causal mixer streams with a fixed latency through mst_tcn_lookahead_* below.  Not built:
+ * f16x3 streaming, gradients.
  * ------------------------------------------------------------------------------------------ */
 size_t mst_tcn_stream_state_bytes(const mst_tcn* tcn, int B, int max_block);
 size_t mst_tcn_stream_workspace_bytes(const mst_tcn* tcn, int B, int max_block);
@@ -690,6 +691,29 @@ int mst_tcn_stream_push(const mst_tcn* tcn, void* state, size_t state_bytes, int
  * offline kernel's 64 / 128.  Short blocks get the smaller tiles, so that they are spread over the chip's SIMDs; the result
  * does not depend on the tile.  For the tests and the probe; 0 for a NULL handle or B, N < 1.                            */
 int mst_tcn_stream_samples_per_wave(const mst_tcn* tcn, int B, int N);
+
+/* ------------------------------------------------------------------------------------------
+ * Stage C, streaming with a fixed latency: block-wise inference of a NON-CAUSAL mixer (csrc/tcn_lookahead.inc).  Every
+ * layer runs (K-1)*d/2 samples behind its input, so a push of N samples returns the N output samples that lie
+ * latency = (K-1) * (2^num_blocks - 1) samples back: y[i] is the output at time t0 + i - latency, zeros where that time is
+ * outside the clip.  The stream has an end: drain pushes (t_end >= 0) feed "after the end" until the last `latency` samples
+ * are out.  The outputs of all pushes, delayed by the latency, are the mst_tcn_forward result of the whole clip BIT FOR BIT,
+ * whatever the block sizes, for a clip of any length (no H_padded * T limit; the state does not depend on T).  A causal mixer is
+ * accepted: latency 0, the result of mst_tcn_stream_push.  State: that of the causal stream (same rings) plus a delay ring
+ * of x, [B][8][cap_x] floats with cap_x the power of two >= latency + max_block.  No allocation, no host synchronisation,
+ * 2 * num_blocks + 2 launches per push.  Refusals as for the causal stream, except the one of a non-causal mixer.
+ * ------------------------------------------------------------------------------------------ */
+/* (K-1) * (2^num_blocks - 1) samples; 0 for a causal mixer; -1 for a NULL handle. */
+long long mst_tcn_lookahead_latency(const mst_tcn* tcn);
+size_t mst_tcn_lookahead_state_bytes(const mst_tcn* tcn, int B, int max_block);
+/* Zeroes every ring and folds the BatchNorm / FiLM table, as mst_tcn_stream_reset. */
+int mst_tcn_lookahead_reset(const mst_tcn* tcn, void* state, size_t state_bytes, int B, int max_block, const float* film,
+                            void* stream);
+/* t0: samples pushed since the reset, drain pushes included (the caller counts; 64-bit).  t_end < 0: the stream is open and
+ * x: dev [B][8][N] holds its next N samples.  t_end >= 0: the stream's length is t_end, every sample of it has been pushed
+ * (t0 >= t_end is required) and this is a drain push: x is not read and may be NULL.  y: dev [B][8][N], may not alias x.   */
+int mst_tcn_lookahead_push(const mst_tcn* tcn, void* state, size_t state_bytes, int B, int max_block, long long t0,
+                           long long t_end, const float* x, int N, float* y, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Stage C, training: the mixer in train() mode and its backward (src/train_style_transfer.py:255-317,

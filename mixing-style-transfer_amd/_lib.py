@@ -268,6 +268,11 @@ SYMBOLS = {
     "mst_tcn_stream_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mst_tcn_stream_samples_per_wave": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "mst_tcn_lookahead_latency": (C.c_longlong, [C.c_void_p]),
+    "mst_tcn_lookahead_state_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "mst_tcn_lookahead_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "mst_tcn_lookahead_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_longlong, C.c_longlong,
+                                         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "mst_tcn_update_params": (C.c_int, [C.c_void_p, C.POINTER(TcnWeights), C.c_void_p]),
     "mst_tcn_train_save_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_longlong]),
     "mst_tcn_train_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_longlong]),

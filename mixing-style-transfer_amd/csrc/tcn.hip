@@ -544,3 +544,4 @@ int mst_tcn_film_forward(const mst_tcn_film* f, const float* emb, int B, float* 
 #include "tcn_f16x3.inc"
 #include "tcn_train.inc"
 #include "tcn_stream.inc"
+#include "tcn_lookahead.inc"

@@ -168,7 +168,8 @@ long long stream_cap(const mst_tcn* h, int r, int max_block) {
 int stream_shape_ok(const mst_tcn* h, int B, int max_block, const char* who) {
   MST_REQUIRE(h, "%s: NULL handle", who);
   MST_REQUIRE(h->cfg.causal, "%s: streaming needs a causal mixer; a non-causal one looks ahead ((K - 1) * d) / 2 samples per layer, "
-              "which a block-wise call does not have: evaluate whole clips with mst_tcn_forward", who);
+              "which a block-wise call does not have: evaluate whole clips with mst_tcn_forward, or stream with a fixed latency "
+              "through mst_tcn_lookahead_push", who);
   MST_REQUIRE(h->mode == MST_TCN_FP32, "%s: the handle is in MST_TCN_F16X3 mode, whose per-clip range scale is a function of the whole "
               "clip: call mst_tcn_set_precision(MST_TCN_FP32) before streaming", who);
   MST_REQUIRE(B >= 1 && B <= 65535, "%s: B must be in 1..65535, got %d", who, B);

@@ -22,7 +22,9 @@ Same class names, constructor arguments, defaults and `state_dict` keys as the r
 
 `TCNMixer.stream()` returns a `TCNStream`: block-wise inference of a causal mixer on audio as it arrives (`push`, `reset`,
 `position`), on the kernels of `csrc/tcn_stream.inc` with `backend = "hip"` (bit-equal to the whole-clip forward whatever the
-block sizes) or on history tensors with `backend = "torch"`.
+block sizes) or on history tensors with `backend = "torch"`.  `TCNMixer.lookahead_stream()` returns a `TCNLookaheadStream`: the
+same for a NON-CAUSAL mixer with the fixed latency (K-1) * (2**num_blocks - 1) samples (`push`, `flush`, `reset`, `latency`), on the
+kernels of `csrc/tcn_lookahead.inc`; `TCNMixer.forward_blockwise` runs a clip of any length through it (state independent of T).
 
 `optimize_tcn_style_transfer` is the reference's per-pair fit (inference/test_tcn_style_transfer.py:84-201) on these backends and
 `mst_amd.optim`, without a host synchronisation inside its loop.
@@ -557,6 +559,45 @@ class TCNMixer(nn.Module):
         takes them, fixed until the next `reset`."""
         return TCNStream(self, batch_size, max_block, film_params)
 
+    def lookahead_stream(self, batch_size=1, max_block=4096, film_params=None):
+        """A `TCNLookaheadStream`: block-wise inference of this mixer, non-causal included, with the fixed latency
+        (K-1) * (2**num_blocks - 1) samples (0 for a causal mixer) and a `flush()` at the clip's end."""
+        return TCNLookaheadStream(self, batch_size, max_block, film_params)
+
+    def forward_blockwise(self, x, film_params=None, block=65536):
+        """`forward(x, film_params)` of a clip (B, 8, T) of any length, computed in blocks of `block` samples through the
+        lookahead stream (`stream()` for a causal mixer): the state does not grow with T and T has no 2^31 limit.  On
+        `backend="hip"` the bits of `forward`."""
+        if x.dim() != 3 or x.shape[1] != self.in_channels:
+            raise ValueError(f"expected (B, {self.in_channels}, T) stems, got {tuple(x.shape)}")
+        if int(block) < 1:
+            raise ValueError(f"TCNMixer.forward_blockwise: block must be positive, got {block}")
+        B, _, T = x.shape
+        y = torch.empty_like(x)
+        if B == 0 or T == 0:
+            return y
+        block = min(int(block), T)
+        if self.causal:
+            s = self.stream(batch_size=B, max_block=block, film_params=film_params)
+            for t in range(0, T, block):
+                y[:, :, t:t + block] = s.push(x[:, :, t:t + block])
+            return y
+        s = self.lookahead_stream(batch_size=B, max_block=block, film_params=film_params)
+        at = -s.latency   # time of the next output sample
+
+        def put(piece, at):
+            n = piece.shape[2]
+            lo, hi = max(at, 0), min(at + n, T)
+            if hi > lo:
+                y[:, :, lo:hi] = piece[:, :, lo - at:hi - at]
+            return at + n
+
+        for t in range(0, T, block):
+            at = put(s.push(x[:, :, t:t + block]), at)
+        for piece in s._drain():
+            at = put(piece, at)
+        return y
+
     def process_stems_dict(self, stems_dict, film_params=None):
         stacked = torch.cat([stems_dict[s] for s in STEM_ORDER], dim=0).unsqueeze(0)
         out = self.forward(stacked, film_params=film_params).squeeze(0)
@@ -587,13 +628,16 @@ class TCNStream:
         self.reset(film_params)
 
     # ---- what both backends refuse -----------------------------------------------------------------------------------
+    _name, _needs_causal = "TCNStream", True    # (TCNLookaheadStream overrides both)
+
     def _check_mixer(self, what):
         m = self.mixer
         if m.backend not in _MIXER_BACKENDS:
             raise ValueError("backend must be 'hip' (default), 'torch' or 'hip-train'")
-        if not m.causal:
+        if self._needs_causal and not m.causal:
             raise RuntimeError(f"{what}: streaming needs a causal mixer (causal=True); a non-causal one looks ahead ((K-1)*d)//2 "
-                               f"samples per layer, which a block-wise call does not have: evaluate whole clips with TCNMixer.forward")
+                               f"samples per layer, which a block-wise call does not have: evaluate whole clips with TCNMixer.forward, "
+                               f"or stream with a fixed latency through TCNMixer.lookahead_stream")
         if m.backend == "hip-train":
             raise RuntimeError(f"{what}: backend='hip-train' is the training path and streaming is inference only; set "
                                f"backend='hip' (or 'torch')")
@@ -618,9 +662,9 @@ class TCNStream:
         """Zero history; new FiLM parameters if given (else those of the last reset); `position` = sample index of the next
         push.  Binds the mixer's current parameters and buffers."""
         m = self.mixer
-        self._check_mixer("TCNStream.reset")
+        self._check_mixer(f"{self._name}.reset")
         if int(position) < 0:
-            raise ValueError(f"TCNStream.reset: position must not be negative, got {position}")
+            raise ValueError(f"{self._name}.reset: position must not be negative, got {position}")
         film_params = self._film_params if film_params is None else film_params
         if m.use_film:
             if film_params is None:
@@ -638,24 +682,9 @@ class TCNStream:
         self.position = int(position)
 
     def _reset_hip(self, film_params):
-        m, B = self.mixer, self.batch_size
-        what = "TCNStream.reset"
-        fl = [p[k] for p in film_params for k in _FILM_KEYS] if m.use_film else []
-        dev = m.input_conv.weight.device
-        msg = _tensor_refusal(what, m.input_conv.weight, *fl)
-        if msg is None and any(t.device != dev for t in fl):
-            msg = f"{what}: the mixer is on {dev} and a FiLM tensor on another device; the kernels need one device"
-        if msg:
-            _raise_refusal(msg)
-        h = m._handle(dev)
-        film = _packed_film(film_params, B, m.num_blocks, m.hidden_channels) if m.use_film else None
-        if film is not None and tuple(film.shape) != (B, m.num_blocks, 4, m.hidden_channels):
-            raise ValueError(f"expected FiLM tensors of shape ({B}, {m.hidden_channels}), got a stack of {tuple(film.shape)}")
-        L = _lib.lib()
+        h, film, dev = self._reset_hip_args(film_params)
+        B, L = self.batch_size, _lib.lib()
         with torch.cuda.device(dev):
-            if getattr(h, "precision", "fp32") != "fp32":
-                _lib.check(L.mst_tcn_set_precision(h.ptr, _PRECISIONS["fp32"], _lib.stream_ptr(dev)), "mst_tcn_set_precision")
-                h.precision = "fp32"
             nstate = L.mst_tcn_stream_state_bytes(h.ptr, B, self.max_block)
             nwork = L.mst_tcn_stream_workspace_bytes(h.ptr, B, self.max_block)
             if nstate == 0 or nwork == 0:
@@ -668,33 +697,62 @@ class TCNStream:
                                               _lib.stream_ptr(dev)), "mst_tcn_stream_reset")
         self._handle = h   # (keeps the C handle alive while the stream uses it)
 
+    def _reset_hip_args(self, film_params):
+        """The handle in fp32 mode, the packed FiLM tensor (or None) and the device of a reset on the kernels."""
+        m, B = self.mixer, self.batch_size
+        what = f"{self._name}.reset"
+        fl = [p[k] for p in film_params for k in _FILM_KEYS] if m.use_film else []
+        dev = m.input_conv.weight.device
+        msg = _tensor_refusal(what, m.input_conv.weight, *fl)
+        if msg is None and any(t.device != dev for t in fl):
+            msg = f"{what}: the mixer is on {dev} and a FiLM tensor on another device; the kernels need one device"
+        if msg:
+            _raise_refusal(msg)
+        h = m._handle(dev)
+        film = _packed_film(film_params, B, m.num_blocks, m.hidden_channels) if m.use_film else None
+        if film is not None and tuple(film.shape) != (B, m.num_blocks, 4, m.hidden_channels):
+            raise ValueError(f"expected FiLM tensors of shape ({B}, {m.hidden_channels}), got a stack of {tuple(film.shape)}")
+        with torch.cuda.device(dev):
+            if getattr(h, "precision", "fp32") != "fp32":
+                _lib.check(_lib.lib().mst_tcn_set_precision(h.ptr, _PRECISIONS["fp32"], _lib.stream_ptr(dev)), "mst_tcn_set_precision")
+                h.precision = "fp32"
+        return h, film, dev
+
+    def _check_bound(self, what):
+        """The mixer is still one the stream can run, and the one it was bound to."""
+        m = self.mixer
+        self._check_mixer(what)
+        if m.backend != self._backend or _state_key(m) != self._key:
+            raise RuntimeError(f"{what}: the mixer's backend, parameters or buffers changed since the stream was bound "
+                               "(load_state_dict, .to(), an in-place edit, an optimiser step); the carried history and the folded "
+                               "BatchNorm / FiLM table belong to the old ones: call reset()")
+
     def push(self, x):
         """x (B, 8, N), 1 <= N <= max_block -> (B, 8, N), the next N output samples."""
         m = self.mixer
-        self._check_mixer("TCNStream.push")
-        if m.backend != self._backend or _state_key(m) != self._key:
-            raise RuntimeError("TCNStream.push: the mixer's backend, parameters or buffers changed since the stream was bound "
-                               "(load_state_dict, .to(), an in-place edit, an optimiser step); the carried history and the folded "
-                               "BatchNorm / FiLM table belong to the old ones: call reset()")
+        self._check_bound(f"{self._name}.push")
         if x.dim() != 3 or x.shape[1] != m.in_channels:
             raise ValueError(f"expected (B, {m.in_channels}, N) stems, got {tuple(x.shape)}")
         B, _, N = x.shape
         if B != self.batch_size:
-            raise ValueError(f"TCNStream.push: the stream was made for batch_size={self.batch_size}, got a batch of {B}")
+            raise ValueError(f"{self._name}.push: the stream was made for batch_size={self.batch_size}, got a batch of {B}")
         if N < 1 or N > self.max_block:
-            raise ValueError(f"TCNStream.push: a block holds 1..max_block={self.max_block} samples, got {N}")
+            raise ValueError(f"{self._name}.push: a block holds 1..max_block={self.max_block} samples, got {N}")
         y = self._push_hip(x) if m.backend == "hip" else self._push_torch(x)
         self.position += N
         return y
 
-    def _push_hip(self, x):
-        m = self.mixer
-        msg = _hip_refusal(m, "TCNStream.push", x)
+    def _hip_input(self, x):
+        """x as the kernels take it, or the refusal."""
+        msg = _hip_refusal(self.mixer, f"{self._name}.push", x)
         if msg is None and x.device != self._state.device:
-            msg = f"TCNStream.push: the stream's state is on {self._state.device} and x on {x.device}"
+            msg = f"{self._name}.push: the stream's state is on {self._state.device} and x on {x.device}"
         if msg:
             _raise_refusal(msg)
-        x = x.contiguous()
+        return x.contiguous()
+
+    def _push_hip(self, x):
+        x = self._hip_input(x)
         y = torch.empty_like(x)
         dev, L = x.device, _lib.lib()
         with torch.cuda.device(dev):
@@ -728,6 +786,150 @@ class TCNStream:
                     g = blk.norm2(conv(blk.conv2, F.leaky_relu(g, negative_slope=0.2), 2 * i + 1))
                     h = F.leaky_relu(g + h, negative_slope=0.2)
             return m.output_conv(h) + x
+
+
+class TCNLookaheadStream(TCNStream):
+    """Block-wise inference of a non-causal `TCNMixer` with a fixed latency (`TCNMixer.lookahead_stream`).
+
+    Every layer runs ((K-1)*d)//2 samples behind its input, so `push(x)`, (B, 8, N) with 1 <= N <= max_block, returns the N
+    output samples that lie `latency = (K-1) * (2**num_blocks - 1)` samples back (zeros before the clip's start), and
+    `flush()` ends the clip and returns the last `latency` samples:
+
+        torch.cat(pushes + [flush], 2)[:, :, latency:]  is  mixer(x, film_params)
+
+    for a clip of any length T >= 1, shorter than the latency included: bit for bit on `backend="hip"` (csrc/tcn_lookahead.inc),
+    to rounding on `backend="torch"`.  Rows of every layer outside the clip are zeros of that layer's own input, as the
+    whole-clip forward pads them.  After `flush()` the stream is closed until `reset()`.  A causal mixer has latency 0 and an
+    empty flush.  Backend rules, FiLM and the binding of the mixer's parameters are those of `TCNStream`; the state does not
+    depend on the clip's length.  `position`: samples pushed since position 0."""
+
+    _name, _needs_causal = "TCNLookaheadStream", False
+
+    @property
+    def latency(self):
+        m = self.mixer
+        return 0 if m.causal else (m.kernel_size - 1) * (2 ** m.num_blocks - 1)
+
+    def reset(self, film_params=None, position=0):
+        """Zero history and an open stream; new FiLM parameters if given (else those of the last reset); `position` = sample
+        index of the next push (a label: the clip starts at the reset).  Binds the mixer's current parameters and buffers."""
+        super().reset(film_params, position)
+        self._xdelay = None
+        self._pushed, self._closed = 0, False   # samples since the reset, drained ones included; flush() was called
+
+    def _reset_hip(self, film_params):
+        h, film, dev = self._reset_hip_args(film_params)
+        B, L = self.batch_size, _lib.lib()
+        with torch.cuda.device(dev):
+            nstate = L.mst_tcn_lookahead_state_bytes(h.ptr, B, self.max_block)
+            if nstate == 0:
+                _lib.check(-1, "mst_tcn_lookahead_state_bytes")
+            if self._state is None or self._state.numel() != nstate or self._state.device != dev:
+                self._state = None
+                self._state = torch.empty(nstate, device=dev, dtype=torch.uint8)
+            _lib.check(L.mst_tcn_lookahead_reset(h.ptr, _lib.dptr(self._state), nstate, B, self.max_block, _lib.dptr(film),
+                                                 _lib.stream_ptr(dev)), "mst_tcn_lookahead_reset")
+        self._handle = h   # (keeps the C handle alive while the stream uses it)
+
+    def _check_bound(self, what):
+        super()._check_bound(what)
+        if self._closed:
+            raise RuntimeError(f"{what}: flush() closed the stream (the clip has ended and its last samples were drained); "
+                               f"call reset() to start the next clip")
+
+    def push(self, x):
+        """x (B, 8, N), 1 <= N <= max_block -> (B, 8, N): the output samples at position - latency ... (zeros before the start)."""
+        y = super().push(x)
+        self._pushed += x.shape[2]
+        return y
+
+    def _push_hip(self, x):
+        return self._step_hip(self._hip_input(x), x.shape[2], -1)
+
+    def _push_torch(self, x):
+        return self._step_torch(x, x.shape[2], None)
+
+    def _drain(self):
+        """Closes the stream and yields the last `latency` output samples in pieces of at most max_block."""
+        m = self.mixer
+        self._check_bound("TCNLookaheadStream.flush")
+        if m.backend == "hip":
+            msg = _hip_refusal(m, "TCNLookaheadStream.flush")
+            if msg:
+                _raise_refusal(msg)
+        self._closed = True
+        end, done = self._pushed, 0
+        while done < self.latency:
+            n = min(self.max_block, self.latency - done)
+            yield (self._step_hip(None, n, end) if m.backend == "hip" else self._step_torch(None, n, end))
+            self._pushed += n
+            done += n
+
+    def flush(self):
+        """Ends the clip: (B, 8, latency), the output samples that the pushes still owe.  Closes the stream."""
+        pieces = list(self._drain())
+        if pieces:
+            return torch.cat(pieces, 2)
+        w = self.mixer.input_conv.weight
+        return w.new_zeros(self.batch_size, self.mixer.in_channels, 0)
+
+    def _step_hip(self, x, N, t_end):
+        dev, L = self._state.device, _lib.lib()
+        y = torch.empty(self.batch_size, self.mixer.in_channels, N, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.check(L.mst_tcn_lookahead_push(self._handle.ptr, _lib.dptr(self._state), self._state.numel(), self.batch_size,
+                                                self.max_block, self._pushed, t_end, _lib.dptr(x), N, _lib.dptr(y),
+                                                _lib.stream_ptr(dev)), "mst_tcn_lookahead_push")
+        return y
+
+    def _step_torch(self, x, N, t_end):
+        """The causal restatement's history tensors on the delayed timeline: ring r runs L_r samples behind the input, rows
+        whose time is outside the clip are zeroed, and the two residuals are read at the lag of the row they are added to."""
+        m, film, t0 = self.mixer, self._film_params, self._pushed
+        w = m.input_conv.weight
+        K, B = m.kernel_size, self.batch_size
+        with torch.no_grad():
+            if x is None:
+                x = w.new_zeros(B, m.in_channels, N)
+            if self._hist is None:
+                self._hist = [x.new_zeros(B, m.hidden_channels, (K - 1) * 2 ** (i // 2)) for i in range(2 * m.num_blocks)]
+                self._xdelay = x.new_zeros(B, m.in_channels, self.latency)
+
+            def clip(v, lag):   # rows of this push at the times t0 - lag + i: zeros outside [0, t_end)
+                lo = min(max(lag - t0, 0), N)
+                hi = N if t_end is None else min(max(t_end - t0 + lag, 0), N)
+                if lo > 0 or hi < N:
+                    v = v.clone()
+                    v[:, :, :lo] = 0
+                    v[:, :, max(hi, lo):] = 0
+                return v
+
+            def conv(c, h, i):   # the causal convolution on (its history, the block); returns z for the delayed residual
+                z = torch.cat([self._hist[i], h], dim=2)
+                self._hist[i] = z[:, :, N:]
+                return F.conv1d(z, c.conv.weight, c.conv.bias, dilation=c.conv.dilation), z
+
+            lag = 0
+            h = clip(m.input_conv(x), lag)
+            for i, blk in enumerate(m.blocks):
+                hist = (K - 1) * 2 ** i
+                pad = 0 if m.causal else hist // 2
+                g, z = conv(blk.conv1, h, 2 * i)
+                res = z[:, :, hist - 2 * pad:hist - 2 * pad + N]   # h delayed by the two lags it skips
+                g = blk.norm1(g)
+                if m.use_film:
+                    p = film[i]
+                    g = clip(F.leaky_relu(p["gamma1"].unsqueeze(-1) * g + p["beta1"].unsqueeze(-1), negative_slope=0.2), lag + pad)
+                    g = blk.norm2(conv(blk.conv2, g, 2 * i + 1)[0])
+                    h = F.leaky_relu(p["gamma2"].unsqueeze(-1) * g + p["beta2"].unsqueeze(-1), negative_slope=0.2) + res
+                else:
+                    g = blk.norm2(conv(blk.conv2, clip(F.leaky_relu(g, negative_slope=0.2), lag + pad), 2 * i + 1)[0])
+                    h = F.leaky_relu(g + res, negative_slope=0.2)
+                lag += 2 * pad
+                h = clip(h, lag)
+            zx = torch.cat([self._xdelay, x], dim=2)
+            self._xdelay = zx[:, :, N:]
+            return clip(m.output_conv(h) + zx[:, :, :N], lag)
 
 
 class _TCNTrainFn(torch.autograd.Function):
@@ -780,16 +982,18 @@ def create_tcn_mixer(receptive_field_seconds=5.2, sample_rate=44100, use_film=Fa
                     use_film=use_film)
 
 
-def apply_style_transfer(tcn, film_generator, stems_input, target_embedding, input_embedding, device):
-    """Processed stems and their mixture for one track (inference_e2e_style_transfer.py:124-177)."""
+def apply_style_transfer(tcn, film_generator, stems_input, target_embedding, input_embedding, device, block=None):
+    """Processed stems and their mixture for one track (inference_e2e_style_transfer.py:124-177).  `block`: run the mixer
+    through `forward_blockwise(block=block)` (whole songs: state independent of the length) in place of `forward`."""
     tcn.eval()
     film_generator.eval()
     with torch.no_grad():
         stems = {k: v.to(device) for k, v in stems_input.items()}
         x = torch.cat([stems[s] for s in STEM_ORDER], dim=0).unsqueeze(0)
         emb = torch.cat([input_embedding.unsqueeze(0), target_embedding.unsqueeze(0)], dim=1).to(device)
-        y = tcn(x, film_params=film_generator(emb))
-        out = {s: y[0, 2 * i:2 * i + 2, :].cpu() for i, s in enumerate(STEM_ORDER)}
+        film = film_generator(emb)
+        y = tcn(x, film_params=film) if block is None else tcn.forward_blockwise(x, film_params=film, block=block)
+        out ={s: y[0, 2 * i:2 * i + 2, :].cpu() for i, s in enumerate(STEM_ORDER)}
         mixture = sum(out.values())
     return {"processed_stems": out, "processed_mixture": mixture}
 
